@@ -5,6 +5,11 @@ parameter manager (BASELINE.json north-star config: "Pull+Push ops/sec
 graph").
 
 Run:  python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints one JSON
+result line. `--full` adds the secondary measurements (today: the
+classic pull/kernel/push path sampled next to the fused step).
+`--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy so two builds can be compared output for output.
 Multi-GPU: launched by the driver via torch.distributed.run (one rank per
 GPU over RCCL); reads RANK/WORLD_SIZE/MASTER_* from the env.
 
@@ -22,6 +27,34 @@ import time
 
 import numpy as np
 import torch
+
+
+DUMP_SAMPLE_ROWS = 2048  # x 2*dim fp32: 8 MB at the default dim
+DUMP_LR = 0.0            # learning rate of a --dump-outputs run
+
+
+def dump_outputs(out_dir, model, worker, loss, triples):
+    """Write what the last timed step handed back: its per-sample loss,
+    and the rows it updated in the store ([embedding | AdaGrad state] per
+    key), sampled with a fixed seed from the step's s/r/o keys.
+
+    A dump run steps with learning rate 0 (see DUMP_LR in main), so the
+    loss is exact run to run and the accumulator halves of the rows
+    differ only by the order of their float additions."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().float().cpu().numpy().astype(np.float32))
+    keys = np.unique(np.concatenate(model.keys_of(triples)))
+    if len(keys) > DUMP_SAMPLE_ROWS:
+        pick = np.random.default_rng(20240607).choice(len(keys), DUMP_SAMPLE_ROWS,
+                                                      replace=False)
+        keys = keys[np.sort(pick)]
+    keys = np.ascontiguousarray(keys, dtype=np.int64)
+    rows = np.zeros((len(keys), model.cfg.row), dtype=np.float32)
+    worker.pull(keys, rows)
+    np.save(os.path.join(out_dir, "updated_rows.npy"), rows)
+    # keys < 2^53, exact in float64
+    np.save(os.path.join(out_dir, "updated_row_keys.npy"), keys.astype(np.float64))
 
 
 def main():
@@ -63,7 +96,21 @@ def main():
                          "ordered unit per channel in parallel — 4 measured +5%% "
                          "over 2 on the 2-rank rehearsal)")
     ap.add_argument("--capacity-factor", type=float, default=3.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements that the headline "
+                         "figure does not need (classic-path reference sample)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step "
+                         "computed as DIR/<name>.npy (float32/float64): its "
+                         "per-sample loss and a fixed seeded sample of the rows it "
+                         "updated. With the same arguments the inputs are identical "
+                         "from run to run (seeded init, batches and negatives; the "
+                         "sustained warmup then always runs --warmup-cap-steps) and "
+                         "the run steps with learning rate 0, at which the lock-free "
+                         "step gives the same results every run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
@@ -84,7 +131,23 @@ def main():
     cfg = ComplExConfig(num_entities=args.entities, num_relations=args.relations,
                         dim=args.dim, neg_samples=args.neg, batch_size=args.batch,
                         lookahead=args.lookahead, seed=7)
+    if args.dump_outputs is not None:
+        # The step is lock-free (Hogwild): samples of one batch that share
+        # a row (every relation row is shared by ~16) read it while others
+        # atomically update it, in whatever order the blocks happen to
+        # run. With a nonzero learning rate that order moves embeddings by
+        # +-lr per element, so two runs of one build drift apart (measured:
+        # per-sample loss off by 0.3 after one step). A dump run therefore
+        # executes the identical kernels on the identical keys with the
+        # learning rate set to 0: every score, loss, gradient and AdaGrad
+        # accumulator update is still computed and applied, the embedding
+        # deltas are exact zeros, and the results are a pure function of
+        # the seeded inputs (accumulators up to float summation order).
+        cfg.lr = DUMP_LR
     model = ComplEx(cfg, server, worker)
+    # seeded init: every run with the same arguments starts from the same
+    # embeddings (init_embeddings draws them with torch's generators)
+    torch.manual_seed(cfg.seed + rank)
     t0 = time.time()
     model.init_embeddings()
     init_s = time.time() - t0
@@ -161,8 +224,9 @@ def main():
 
     # driver-contract warmup (the W untimed steps), timed for the cold rate
     t_cold = time.perf_counter()
+    warm_out = None
     for i in range(args.warmup):
-        run_step(i)
+        warm_out = run_step(i)
     model.drain()
     if is_cuda:
         torch.cuda.synchronize()
@@ -178,13 +242,18 @@ def main():
     extra = 0
     recent = []
     t_w = time.perf_counter()
+    # (with --dump-outputs the step count must not depend on the clock,
+    # or the state the timed steps start from would differ run to run:
+    # always go to the cap, which the 1-GPU default reaches anyway)
+    fixed_warmup = args.dump_outputs is not None
     while extra < args.warmup_cap_steps:
-        if time.perf_counter() - t_w >= args.warmup_budget_s and len(recent) >= 10:
+        if (not fixed_warmup and time.perf_counter() - t_w >= args.warmup_budget_s
+                and len(recent) >= 10):
             window = recent[-10:]
             if max(window) <= 1.25 * min(window):
                 break
         t_s = time.perf_counter()
-        run_step(step_i)
+        warm_out = run_step(step_i)
         if is_cuda:
             torch.cuda.synchronize()
         recent.append(time.perf_counter() - t_s)
@@ -192,11 +261,11 @@ def main():
         extra += 1
     model.drain()
 
-    # classic-path reference sample (untimed region): the fused
-    # slab-direct step is the world==1 hot path; the classic
+    # classic-path reference sample (untimed region, --full only): the
+    # fused slab-direct step is the world==1 hot path; the classic
     # pull/kernel/push path is what runs at world>1, so report both
     classic_ops_per_s = None
-    if use_fused and world == 1:
+    if args.full and use_fused and world == 1:
         for _ in range(2):
             model.train_batch(get_batch(step_i))
             worker.advance_clock()
@@ -210,6 +279,12 @@ def main():
         torch.cuda.synchronize()
         classic_ops_per_s = keys_per_step * 6 / (time.perf_counter() - t_c)
 
+    # the timed region ends with one read-back of the last step's loss:
+    # do the same once here, so its reduction kernel is loaded before the
+    # clock starts (the first launch costs ~3.5 ms, 15% of a 20-step run)
+    if warm_out is not None and warm_out.numel():
+        float(warm_out.mean().item())
+
     if prof is not None:
         prof.enable()
 
@@ -218,9 +293,12 @@ def main():
     if is_cuda:
         torch.cuda.synchronize()
     t_start = time.perf_counter()
-    last_loss = 0.0
+    last_out = None
     for j in range(args.steps):
-        last_loss = run_step(step_i + j, sync_loss=(j == args.steps - 1))
+        last_out = run_step(step_i + j)
+    # the last step's loss is read back inside the timed region (one
+    # host sync per run, as a training loop that logs its loss does)
+    last_loss = float(last_out.mean().item()) if last_out.numel() else 0.0
     model.drain()
     if is_cuda:
         torch.cuda.synchronize()
@@ -234,6 +312,12 @@ def main():
     # MAX elapsed over ranks
     if world > 1:
         t_elapsed = worker.allreduce(t_elapsed, op="max")
+
+    if args.dump_outputs is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, model, worker, last_out,
+                         get_batch(step_i + args.steps - 1))
+        worker.barrier()
 
     ops_total = keys_per_step * args.steps * world
     ops_per_s = ops_total / t_elapsed
@@ -282,6 +366,7 @@ def main():
                 "cold_ops_per_s": cold_ops_per_s,
                 "classic_ops_per_s": classic_ops_per_s,
                 "last_loss": last_loss,
+                "lr": cfg.lr,
                 "pull_local_frac": st["pull_local"] / max(1, st["pull_keys"]),
                 "push_local_frac": st["push_local"] / max(1, st["push_keys"]),
             },

@@ -36,7 +36,7 @@ def test_simple_ws3():
     run_dist(3, _simple_dist, timeout=180)
 
 
-def _w2v(device):
+def _w2v(device, tmp_path):
     adapm = _fresh()
     from adapm_amd.models.word2vec import (W2VConfig, Word2Vec,
                                            make_synthetic_sentences, syn0)
@@ -61,7 +61,7 @@ def _w2v(device):
         epoch_losses.append(float(np.mean(ls)))
     model.drain()
     assert epoch_losses[-1] < epoch_losses[0], f"no learning {epoch_losses}"
-    path = "/tmp/w2v_test.txt"
+    path = str(tmp_path / "w2v_test.txt")
     model.export_text(path, max_words=10)
     lines = open(path).read().splitlines()
     assert lines[0] == "10 32" and len(lines) == 11
@@ -70,13 +70,13 @@ def _w2v(device):
     server.shutdown()
 
 
-def test_w2v_cpu():
-    _w2v("cpu")
+def test_w2v_cpu(tmp_path):
+    _w2v("cpu", tmp_path)
 
 
 @pytest.mark.gpu
-def test_w2v_gpu():
-    _w2v("cuda:0")
+def test_w2v_gpu(tmp_path):
+    _w2v("cuda:0", tmp_path)
 
 
 def _mf(device, schedule):

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 
-def _run_kge(device):
+def _run_kge(device, tmp_path):
     import adapm_amd
     from adapm_amd.models.kge import ComplEx, ComplExConfig, make_synthetic_triples
 
@@ -51,7 +51,7 @@ def _run_kge(device):
     assert e1["mrr"] >= e2["mrr"] - 1e-9
 
     # checkpoint round-trip
-    path = "/tmp/kge_ckpt_test.npz"
+    path = str(tmp_path / "kge_ckpt_test.npz")
     model.save_checkpoint(path)
     before = np.zeros((4, cfg.row), dtype=np.float32)
     worker.pull(np.arange(4, dtype=np.int64), before)
@@ -67,13 +67,13 @@ def _run_kge(device):
     server.shutdown()
 
 
-def test_kge_model_cpu():
-    _run_kge("cpu")
+def test_kge_model_cpu(tmp_path):
+    _run_kge("cpu", tmp_path)
 
 
 @pytest.mark.gpu
-def test_kge_model_gpu():
-    _run_kge("cuda:0")
+def test_kge_model_gpu(tmp_path):
+    _run_kge("cuda:0", tmp_path)
 
 
 def _kge_dist(rank, world):

@@ -2651,6 +2651,50 @@ class Server {
   // classic pull/kernel/push path remains the general case. Counts the
   // same pull+push key-ops in the stats (the store IS read and updated
   // per key).
+  //
+  // When may the step write rows that are unique in its batch with plain
+  // stores? A plain read-modify-write loses any update that lands on the
+  // row between its read and its write, so nothing else may write the
+  // slab while the launch runs. At world==1 the slab is written only by
+  // worker ops (push / set / fused steps), each enqueued by the calling
+  // thread on that thread's current stream: there are no peers, so the
+  // sync thread has nothing to merge, and rebalance_spill quiesces the
+  // workers and clears layout_identity_, after which kge_step_fused
+  // refuses to run. Ops on one stream are serialized by the stream. So
+  // the plain path is taken only while
+  //   (a) the server was set up for a single worker thread (a second
+  //       worker could push on its own stream at any time), and
+  //   (b) every fused step so far came in on one stream, the one that
+  //       owns the row marks. The first call on another stream waits for
+  //       the owner stream to drain and turns the plain path off for good.
+  // Every other call runs the all-atomic kernel, which tolerates
+  // concurrent writers. (One worker thread that pushes on a second stream
+  // without synchronizing it with the first has no order between its own
+  // ops, with or without this.) Called with fused_mu_ held; allocates the
+  // marks (2 bits per key, zeroed once) on first use.
+  bool fused_plain_ok(void* st) {
+    if (clocks_.size() != 1 || fused_multi_stream_) return false;
+    if (!fused_marks_.defined()) {
+      if (getenv("ADAPM_FUSED_ATOMIC")) {  // A/B switch: keep the all-atomic kernel
+        fused_multi_stream_ = true;
+        return false;
+      }
+      fused_marks_ = torch::zeros({rowmark_words(num_keys_)},
+                                  torch::TensorOptions().dtype(torch::kInt32).device(dev_));
+      if (getenv("ADAPM_FUSED_STATS"))
+        fused_shared_stat_ =
+            torch::zeros({1}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
+      fused_marks_stream_ = st;
+      return true;
+    }
+    if (st == fused_marks_stream_) return true;
+#ifdef ADAPM_WITH_HIP
+    hipStreamSynchronize((hipStream_t)fused_marks_stream_);
+#endif
+    fused_multi_stream_ = true;
+    return false;
+  }
+
   torch::Tensor kge_step_fused(torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o,
                                torch::Tensor keys_neg, int64_t N, int64_t D, double lr,
                                double eps) {
@@ -2672,13 +2716,42 @@ class Server {
     auto kr = keys_r.to(dev_, true);
     auto ko = keys_o.to(dev_, true);
     auto kn = keys_neg.to(dev_, true);
+    void* st = current_stream(dev_);
     {
       InflightGuard g(this);
-      kge_complex_step_fused_gpu(slab_.data, ks.data_ptr<int64_t>(), kr.data_ptr<int64_t>(),
-                                 ko.data_ptr<int64_t>(), kn.data_ptr<int64_t>(),
-                                 loss.data_ptr<float>(), (int)B, (int)N, (int)D,
-                                 Slab::padded(uniform_len_), world_, rank_, (float)lr,
-                                 (float)eps, current_stream(dev_));
+      // Here the step diverges from kge_step_fused_general: a row that only
+      // one key occurrence of this batch names is written with plain stores
+      // (fused_plain_ok says when that is safe). The world>1 / offsets-mode
+      // path stays all-atomic: its sync handlers scatter-add into the slab
+      // while the step runs, and a plain read-modify-write would lose them.
+      std::unique_lock<std::mutex> mg(fused_mu_);
+      if (fused_plain_ok(st)) {
+        // pre-pass, step and clean-up are enqueued under the lock: the row
+        // marks are per server, and a second caller must find them zeroed
+        RowMarkKeys mk{{ks.data_ptr<int64_t>(), kr.data_ptr<int64_t>(), ko.data_ptr<int64_t>(),
+                        kn.data_ptr<int64_t>()},
+                       {B, B, B, B * N},
+                       4};
+        auto* marks = reinterpret_cast<uint32_t*>(fused_marks_.data_ptr<int32_t>());
+        rowmark_set_gpu(marks, mk, st);
+        kge_complex_step_fused_gpu(
+            slab_.data, mk.keys[0], mk.keys[1], mk.keys[2], mk.keys[3], loss.data_ptr<float>(),
+            (int)B, (int)N, (int)D, Slab::padded(uniform_len_), world_, rank_, (float)lr,
+            (float)eps, st, marks,
+            fused_shared_stat_.defined()
+                ? reinterpret_cast<unsigned long long*>(fused_shared_stat_.data_ptr<int64_t>())
+                : nullptr);
+        rowmark_clear_gpu(marks, mk, st);
+        stat_fused_plain_ += 1;
+      } else {
+        mg.unlock();
+        kge_complex_step_fused_gpu(slab_.data, ks.data_ptr<int64_t>(), kr.data_ptr<int64_t>(),
+                                   ko.data_ptr<int64_t>(), kn.data_ptr<int64_t>(),
+                                   loss.data_ptr<float>(), (int)B, (int)N, (int)D,
+                                   Slab::padded(uniform_len_), world_, rank_, (float)lr,
+                                   (float)eps, st);
+        stat_fused_atomic_ += 1;
+      }
     }
     int64_t total = 3 * B + B * N;
     stat_pull_keys_ += total;
@@ -3308,6 +3381,16 @@ class Server {
     d["forwards"] = stat_forwards_.load();
     d["dropped_records"] = stat_dropped_records_.load();
     d["delta_overhops"] = stat_delta_overhops_.load();
+    // world==1 fused ComplEx steps by write path, and (ADAPM_FUSED_STATS,
+    // synchronizes) how many key occurrences of the plain-path steps were
+    // shared rows and so stayed on atomics
+    d["fused_plain_steps"] = stat_fused_plain_.load();
+    d["fused_atomic_steps"] = stat_fused_atomic_.load();
+    {
+      std::lock_guard<std::mutex> g(fused_mu_);
+      if (fused_shared_stat_.defined())
+        d["fused_shared_occurrences"] = fused_shared_stat_.cpu().item<int64_t>();
+    }
     {
       py::list hh;
       for (int i = 0; i < 9; ++i) hh.append(hop_hist_[i].load());
@@ -3484,6 +3567,14 @@ class Server {
       stat_relocated_in_{0}, stat_replications_{0}, stat_drops_{0}, stat_forwards_{0},
       stat_dropped_records_{0}, stat_delta_overhops_{0}, stat_bytes_sent_{0},
       stat_bytes_recv_{0}, stat_sampling_checks_{0};
+
+  // world==1 fused step: per-batch row marks (see fused_plain_ok)
+  std::mutex fused_mu_;
+  torch::Tensor fused_marks_;        // int32 words, 2 bits per key, all-zero between steps
+  torch::Tensor fused_shared_stat_;  // int64[1], only with ADAPM_FUSED_STATS
+  void* fused_marks_stream_ = nullptr;
+  bool fused_multi_stream_ = false;
+  std::atomic<int64_t> stat_fused_plain_{0}, stat_fused_atomic_{0};
 };
 
 // ------------------------------------------------------- app kernel wrappers

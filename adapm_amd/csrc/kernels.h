@@ -27,12 +27,37 @@ void kge_complex_step_cpu(const float* s, const float* r, const float* o, const 
                           float* ds, float* dr, float* do_, float* dneg, float* loss,
                           int B, int N, int D, float lr, float eps);
 
+// Row marks for the fused slab-direct steps: which key occurrences of one
+// batch share their slab row with another occurrence of the same batch.
+// `marks` is a zeroed device bitmap of rowmark_words(rows) words, two bits
+// per row. rowmark_set_gpu marks every occurrence of up to four key arrays
+// (counted together, whatever their role); the step kernel then reads
+// "shared or unique" per occurrence; rowmark_clear_gpu, given the same
+// keys, restores the bitmap to all-zero at the cost of the batch, not of
+// the table. All three go on one stream, in that order. Keys must be row
+// indices (single-rank identity layout: row == key).
+struct RowMarkKeys {
+  const int64_t* keys[4];  // DEVICE pointers
+  int64_t n[4];
+  int count;  // arrays in use
+};
+inline int64_t rowmark_words(int64_t rows) { return (rows + 15) / 16; }
+void rowmark_set_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream);
+void rowmark_clear_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream);
+
 // FUSED ComplEx step: reads entity/relation rows DIRECTLY from the slab
-// and atomically accumulates the AdaGrad-transformed deltas back — no
-// intermediate pull/push buffers (the classic path pays a gather write +
-// kernel read + delta write + scatter read; this saves all four).
-// Duplicate keys within the batch see hogwild-style concurrent updates
-// (async-PS semantics). keys_* are DEVICE int64 pointers.
+// and accumulates the AdaGrad-transformed deltas back — no intermediate
+// pull/push buffers (the classic path pays a gather write + kernel read +
+// delta write + scatter read; this saves all four). keys_* are DEVICE
+// int64 pointers.
+// Writes: with `marks` (filled by rowmark_set_gpu for exactly these keys,
+// world == 1 only) plain stores on rows unique in the batch, atomic adds on
+// shared ones — a float atomic costs ~4-5x the plain store of the same
+// bytes and only a shared row needs it. The caller guarantees that nothing
+// else writes the slab while the launch runs. Without marks every write is
+// atomic. Either way duplicate keys within the batch see hogwild-style
+// concurrent updates (async-PS semantics). shared_stat (optional, with
+// marks) accumulates the number of occurrences that took the atomic path.
 // Addressing modes (row_at): world >= 1 — identity layout, key k at
 // (k/world)*plen (single-rank fast path, zero host work); world == 0 —
 // keys_* carry precomputed float OFFSETS into the slab (the world>1 /
@@ -41,7 +66,9 @@ void kge_complex_step_cpu(const float* s, const float* r, const float* o, const 
 void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
                                 const int64_t* keys_o, const int64_t* keys_neg, float* loss,
                                 int B, int N, int D, int32_t plen, int world, int rank,
-                                float lr, float eps, void* stream);
+                                float lr, float eps, void* stream,
+                                const uint32_t* marks = nullptr,
+                                unsigned long long* shared_stat = nullptr);
 
 // CPU tier of the offsets-mode fused steps (exercises the world>1 fused
 // protocol path in the gloo multi-process tests; serial, in-place).
@@ -55,8 +82,10 @@ void mf_update_step_fused_offs_cpu(float* slab, const int64_t* offs_w, const int
                                    const float* x, float* loss, int B, int R, float lr,
                                    float lambda, float eps);
 
-// FUSED SGNS step (same contract as kge_complex_step_fused_gpu: slab-
-// direct reads + atomic AdaGrad writes, hogwild on duplicates).
+// FUSED SGNS step (slab-direct reads + AdaGrad writes like
+// kge_complex_step_fused_gpu, but every write is still atomic: the ComplEx
+// step is plain on rows unique in the batch, atomic on shared ones, and
+// this step can adopt the same row marks).
 void w2v_sgns_step_fused_gpu(float* slab, const int64_t* keys_ctr, const int64_t* keys_ctx,
                              const int64_t* keys_neg, float* loss, int B, int N, int D,
                              int32_t plen, int world, float lr, float eps, void* stream);

@@ -2,8 +2,9 @@
 // 4 waves) per training sample; rows are 2D floats = [emb(D) | accum(D)].
 // These kernels are HBM-bound (each pulled row is read once, each delta
 // row written once); the arithmetic per element is small, so the design
-// goal is coalesced float4 row traffic and cheap block reductions
-// (wave __shfl_xor + one LDS hop across the 4 waves).
+// goal is coalesced row traffic (one dword per lane, 256 contiguous bytes
+// per wave instruction) and cheap block reductions (wave __shfl_xor + one
+// LDS hop across the 4 waves).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
@@ -476,20 +477,96 @@ __device__ inline float* row_at(float* slab, int64_t v, int32_t plen, int world)
   return world ? slab + (v / world) * (int64_t)plen : slab + v;
 }
 
+// ---- per-launch row marks (see kernels.h): two bits per slab row, 16
+// rows per word. Bit 0 = "an occurrence of this batch names the row",
+// bit 1 = "a second one does too".
+__device__ inline uint32_t* rowmark_word(uint32_t* marks, int64_t row) { return marks + (row >> 4); }
+__device__ inline int rowmark_shift(int64_t row) { return 2 * (int)(row & 15); }
+
+__device__ inline int64_t rowmark_key(const RowMarkKeys& ks, int64_t i) {
+  // occurrence i of the concatenated key arrays
+  int a = 0;
+  while (a < ks.count - 1 && i >= ks.n[a]) {
+    i -= ks.n[a];
+    ++a;
+  }
+  return ks.keys[a][i];
+}
+
+__global__ void k_rowmark_set(uint32_t* __restrict__ marks, RowMarkKeys ks, int64_t total) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  int64_t row = rowmark_key(ks, i);
+  uint32_t bit = 1u << rowmark_shift(row);
+  uint32_t old = atomicOr(rowmark_word(marks, row), bit);
+  if ((old & bit) && !(old & (bit << 1))) atomicOr(rowmark_word(marks, row), bit << 1);
+}
+
+// Every word that k_rowmark_set touched held only marks of this batch, so
+// storing 0 over it (possibly from several threads) restores all-zero.
+__global__ void k_rowmark_clear(uint32_t* __restrict__ marks, RowMarkKeys ks, int64_t total) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  *rowmark_word(marks, rowmark_key(ks, i)) = 0u;
+}
+
+void rowmark_set_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream) {
+  int64_t total = 0;
+  for (int a = 0; a < ks.count; ++a) total += ks.n[a];
+  if (total == 0) return;
+  hipLaunchKernelGGL(k_rowmark_set, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
+                     (hipStream_t)stream, marks, ks, total);
+}
+
+void rowmark_clear_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream) {
+  int64_t total = 0;
+  for (int a = 0; a < ks.count; ++a) total += ks.n[a];
+  if (total == 0) return;
+  hipLaunchKernelGGL(k_rowmark_clear, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
+                     (hipStream_t)stream, marks, ks, total);
+}
+
+// UNIQ: is the row shared with another occurrence of this batch? The word
+// address depends only on the key, so this load runs beside the row loads
+// and is uniform across the block.
+template <bool UNIQ>
+__device__ inline bool row_shared(const uint32_t* __restrict__ marks, int64_t key) {
+  if (!UNIQ) return true;
+  return (marks[key >> 4] >> (rowmark_shift(key) + 1)) & 1u;
+}
+
+// row = row + delta with a plain store, rounded exactly like the atomic it
+// replaces: the add must not be contracted into an fma with the multiply
+// that produced delta.
+__device__ inline float plain_add(float a, float delta) {
+#pragma clang fp contract(off)
+  return a + delta;
+}
+
 // Fused ComplEx step — see kernels.h. Structure mirrors k_kge_step but
-// rows come from / return to the slab itself.
-template <int KPT>
+// rows come from / return to the slab itself. UNIQ = false is the
+// all-atomic kernel (marks unused); UNIQ = true writes the rows that
+// `marks` shows to be unique in this batch with plain stores.
+template <int KPT, bool UNIQ>
 __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __restrict__ keys_s,
                                  const int64_t* __restrict__ keys_r,
                                  const int64_t* __restrict__ keys_o,
                                  const int64_t* __restrict__ keys_neg, float* __restrict__ loss,
                                  int B, int N, int D, int32_t plen, int world, int rank,
-                                 float lr, float eps) {
+                                 float lr, float eps, const uint32_t* __restrict__ marks,
+                                 unsigned long long* __restrict__ shared_stat) {
   __shared__ float lds[KT / 64];
   const int dc = D >> 1;
+  // the marks imply the single-rank layout: a constant spares row_at the
+  // 64-bit division
+  const int w = UNIQ ? 1 : world;
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    const float* sb = row_at(slab, keys_s[b], plen, world);
-    const float* rb = row_at(slab, keys_r[b], plen, world);
+    const int64_t key_s = keys_s[b], key_r = keys_r[b];
+    const float* sb = row_at(slab, key_s, plen, w);
+    const float* rb = row_at(slab, key_r, plen, w);
+    const bool s_shared = row_shared<UNIQ>(marks, key_s);
+    const bool r_shared = row_shared<UNIQ>(marks, key_r);
+    unsigned n_shared = (unsigned)s_shared + (unsigned)r_shared;
 
     float s_re[KPT], s_im[KPT], r_re[KPT], r_im[KPT];
     float a_sre[KPT], a_sim[KPT], a_rre[KPT], a_rim[KPT];
@@ -513,15 +590,21 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
     float lsum = 0.f;
     for (int j = 0; j <= N; ++j) {
       int64_t ok = (j == 0) ? keys_o[b] : keys_neg[(int64_t)b * N + (j - 1)];
-      float* ob = row_at(slab, ok, plen, world);
+      float* ob = row_at(slab, ok, plen, w);
+      const bool o_shared = row_shared<UNIQ>(marks, ok);
+      n_shared += (unsigned)o_shared;
       float y = (j == 0) ? 1.f : -1.f;
       float part = 0.f;
-      float o_re[KPT], o_im[KPT];
+      float o_re[KPT], o_im[KPT], Go_re[KPT], Go_im[KPT];
+      // accumulator halves ride with the embedding halves, so their
+      // latency hides behind the block reduction
 #pragma unroll
       for (int i = 0; i < KPT; ++i) {
         int k = threadIdx.x + i * KT;
         o_re[i] = k < dc ? ob[k] : 0.f;
         o_im[i] = k < dc ? ob[dc + k] : 0.f;
+        Go_re[i] = k < dc ? ob[D + k] : 0.f;
+        Go_im[i] = k < dc ? ob[D + dc + k] : 0.f;
         part += u_re[i] * o_re[i] + u_im[i] * o_im[i];
       }
       float psi = block_reduce_sum(part, lds);
@@ -538,12 +621,22 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
         a_rim[i] += c * (s_re[i] * o_im[i] - s_im[i] * o_re[i]);
         float g_re = c * u_re[i];
         float g_im = c * u_im[i];
-        float G_re = ob[D + k] + g_re * g_re;
-        float G_im = ob[D + dc + k] + g_im * g_im;
-        atomicAdd(&ob[k], -lr * g_re * __frsqrt_rn(G_re + eps));
-        atomicAdd(&ob[dc + k], -lr * g_im * __frsqrt_rn(G_im + eps));
-        atomicAdd(&ob[D + k], g_re * g_re);
-        atomicAdd(&ob[D + dc + k], g_im * g_im);
+        float G_re = Go_re[i] + g_re * g_re;
+        float G_im = Go_im[i] + g_im * g_im;
+        float d_re = -lr * g_re * __frsqrt_rn(G_re + eps);
+        float d_im = -lr * g_im * __frsqrt_rn(G_im + eps);
+        if (o_shared) {
+          atomicAdd(&ob[k], d_re);
+          atomicAdd(&ob[dc + k], d_im);
+          atomicAdd(&ob[D + k], g_re * g_re);
+          atomicAdd(&ob[D + dc + k], g_im * g_im);
+        } else {
+          // only writer of this row in this launch: same sums, plain stores
+          ob[k] = plain_add(o_re[i], d_re);
+          ob[dc + k] = plain_add(o_im[i], d_im);
+          ob[D + k] = plain_add(Go_re[i], g_re * g_re);
+          ob[D + dc + k] = plain_add(Go_im[i], g_im * g_im);
+        }
       }
     }
     float* dsb = const_cast<float*>(sb);
@@ -552,33 +645,68 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
     for (int i = 0; i < KPT; ++i) {
       int k = threadIdx.x + i * KT;
       if (k >= dc) continue;
-      float Gsr = sb[D + k] + a_sre[i] * a_sre[i];
-      float Gsi = sb[D + dc + k] + a_sim[i] * a_sim[i];
-      atomicAdd(&dsb[k], -lr * a_sre[i] * __frsqrt_rn(Gsr + eps));
-      atomicAdd(&dsb[dc + k], -lr * a_sim[i] * __frsqrt_rn(Gsi + eps));
-      atomicAdd(&dsb[D + k], a_sre[i] * a_sre[i]);
-      atomicAdd(&dsb[D + dc + k], a_sim[i] * a_sim[i]);
-      float Grr = rb[D + k] + a_rre[i] * a_rre[i];
-      float Gri = rb[D + dc + k] + a_rim[i] * a_rim[i];
-      atomicAdd(&drb[k], -lr * a_rre[i] * __frsqrt_rn(Grr + eps));
-      atomicAdd(&drb[dc + k], -lr * a_rim[i] * __frsqrt_rn(Gri + eps));
-      atomicAdd(&drb[D + k], a_rre[i] * a_rre[i]);
-      atomicAdd(&drb[D + dc + k], a_rim[i] * a_rim[i]);
+      float Gs_re = sb[D + k], Gs_im = sb[D + dc + k];
+      float Gsr = Gs_re + a_sre[i] * a_sre[i];
+      float Gsi = Gs_im + a_sim[i] * a_sim[i];
+      float ds_re = -lr * a_sre[i] * __frsqrt_rn(Gsr + eps);
+      float ds_im = -lr * a_sim[i] * __frsqrt_rn(Gsi + eps);
+      if (s_shared) {
+        atomicAdd(&dsb[k], ds_re);
+        atomicAdd(&dsb[dc + k], ds_im);
+        atomicAdd(&dsb[D + k], a_sre[i] * a_sre[i]);
+        atomicAdd(&dsb[D + dc + k], a_sim[i] * a_sim[i]);
+      } else {
+        dsb[k] = plain_add(s_re[i], ds_re);
+        dsb[dc + k] = plain_add(s_im[i], ds_im);
+        dsb[D + k] = plain_add(Gs_re, a_sre[i] * a_sre[i]);
+        dsb[D + dc + k] = plain_add(Gs_im, a_sim[i] * a_sim[i]);
+      }
+      float Gr_re = rb[D + k], Gr_im = rb[D + dc + k];
+      float Grr = Gr_re + a_rre[i] * a_rre[i];
+      float Gri = Gr_im + a_rim[i] * a_rim[i];
+      float dr_re = -lr * a_rre[i] * __frsqrt_rn(Grr + eps);
+      float dr_im = -lr * a_rim[i] * __frsqrt_rn(Gri + eps);
+      if (r_shared) {
+        atomicAdd(&drb[k], dr_re);
+        atomicAdd(&drb[dc + k], dr_im);
+        atomicAdd(&drb[D + k], a_rre[i] * a_rre[i]);
+        atomicAdd(&drb[D + dc + k], a_rim[i] * a_rim[i]);
+      } else {
+        drb[k] = plain_add(r_re[i], dr_re);
+        drb[dc + k] = plain_add(r_im[i], dr_im);
+        drb[D + k] = plain_add(Gr_re, a_rre[i] * a_rre[i]);
+        drb[D + dc + k] = plain_add(Gr_im, a_rim[i] * a_rim[i]);
+      }
     }
-    if (threadIdx.x == 0) loss[b] = lsum;
+    if (threadIdx.x == 0) {
+      loss[b] = lsum;
+      if (UNIQ && shared_stat) atomicAdd(shared_stat, (unsigned long long)n_shared);
+    }
   }
 }
 
 void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
                                 const int64_t* keys_o, const int64_t* keys_neg, float* loss,
                                 int B, int N, int D, int32_t plen, int world, int rank,
-                                float lr, float eps, void* stream) {
+                                float lr, float eps, void* stream, const uint32_t* marks,
+                                unsigned long long* shared_stat) {
   int dc = D >> 1;
   dim3 g((unsigned)std::min<int64_t>(B, 16384)), t(KT);
   auto st = (hipStream_t)stream;
-#define LAUNCHF(KPT) \
-  hipLaunchKernelGGL(k_kge_step_fused<KPT>, g, t, 0, st, slab, keys_s, keys_r, keys_o, \
-                     keys_neg, loss, B, N, D, plen, world, rank, lr, eps)
+  // marks are indexed by key, which is the row only in the single-rank
+  // identity layout; every other addressing mode stays all-atomic
+  const bool uniq = marks != nullptr && world == 1;
+#define LAUNCHF(KPT)                                                                        \
+  do {                                                                                      \
+    if (uniq)                                                                               \
+      hipLaunchKernelGGL((k_kge_step_fused<KPT, true>), g, t, 0, st, slab, keys_s, keys_r,  \
+                         keys_o, keys_neg, loss, B, N, D, plen, world, rank, lr, eps, marks, \
+                         shared_stat);                                                      \
+    else                                                                                    \
+      hipLaunchKernelGGL((k_kge_step_fused<KPT, false>), g, t, 0, st, slab, keys_s, keys_r, \
+                         keys_o, keys_neg, loss, B, N, D, plen, world, rank, lr, eps,       \
+                         (const uint32_t*)nullptr, (unsigned long long*)nullptr);           \
+  } while (0)
   if (dc <= KT) LAUNCHF(1);
   else if (dc <= 2 * KT) LAUNCHF(2);
   else if (dc <= 4 * KT) LAUNCHF(4);

@@ -139,7 +139,8 @@ class Server:
         d = make_distribution(distribution, min, max, seed=self.rt.rank, counts=counts,
                               power=power, device=self.rt.device)
         self.sampling = SamplingManager(self._s, scheme, with_replacement, d, min, max,
-                                        pool_size=pool_size, reuse_factor=reuse_factor)
+                                        pool_size=pool_size, reuse_factor=reuse_factor,
+                                        device=self.rt.device)
 
     def barrier(self):
         if self.rt.world > 1:

@@ -55,9 +55,12 @@
 #include "common.h"
 #include "kernels.h"
 #include "ops.h"
+#include "ustream.h"
 
 #ifdef ADAPM_WITH_HIP
 #include <c10/hip/HIPStream.h>
+#include <ATen/core/CachingHostAllocator.h>
+#include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #endif
 
 extern "C" {
@@ -273,6 +276,115 @@ struct ChannelState {
   // the >=2nd consecutive globally-idle round (sync thread only writes).
   int64_t idle_streak = 0;
   std::atomic<int64_t> idle2_events{0};
+};
+
+// ------------------------------------------------------- uniform stream
+
+// Native side of sampling.Uniform: continues the numpy PCG64 stream it was
+// imported from, on `device`, key for key and state for state (ustream.h).
+// draw() enqueues on the caller's current stream and never synchronises.
+// The state tensor is read and written by the draws in stream order, so
+// all work on it stays on one stream at a time: a call that arrives on
+// another stream first waits for the previous owner stream to drain (as
+// Server::fused_plain_ok does for the row marks) and then owns it.
+class UniformStream {
+ public:
+  UniformStream(int64_t lo, int64_t hi, const std::string& device)
+      : lo_(lo), hi_(hi), dev_(device) {
+    TORCH_CHECK(supported(lo, hi), "UniformStream: [", lo, ", ", hi,
+                ") is not a range of numpy's 32-bit bounded draw");
+    excl_ = (uint32_t)((uint64_t)hi - (uint64_t)lo);
+    thr_ = (uint32_t)((0x100000000ull - excl_) % excl_);
+    state_ = torch::zeros({USTREAM_STATE_WORDS},
+                          torch::TensorOptions().dtype(torch::kInt64).device(dev_));
+  }
+
+  // numpy takes other code paths for a one-value range (rng == 0), for
+  // rng == 0xFFFFFFFF (raw words) and for anything wider than 32 bits
+  static bool supported(int64_t lo, int64_t hi) {
+    if (hi <= lo || lo == std::numeric_limits<int64_t>::min()) return false;
+    uint64_t span = (uint64_t)hi - (uint64_t)lo;
+    return span >= 2 && span <= 0xFFFFFFFFull;
+  }
+
+  void import_state(uint64_t state_hi, uint64_t state_lo, uint64_t inc_hi, uint64_t inc_lo,
+                    uint64_t has_uint32, uint64_t uinteger) {
+    auto h = torch::empty({USTREAM_STATE_WORDS}, torch::kInt64);
+    uint64_t* p = reinterpret_cast<uint64_t*>(h.data_ptr<int64_t>());
+    p[0] = state_hi, p[1] = state_lo, p[2] = inc_hi, p[3] = inc_lo;
+    p[4] = has_uint32 ? 1 : 0, p[5] = uinteger & 0xFFFFFFFFull;
+    ustream_build_table(p);
+    std::lock_guard<std::mutex> g(mu_);
+    adopt(current_stream(dev_));
+    state_.copy_(h);
+  }
+
+  // one small D2H copy; waits for the draws enqueued so far
+  std::vector<uint64_t> export_state() {
+    torch::Tensor h;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      adopt(current_stream(dev_));
+      h = state_.slice(0, 0, USTREAM_GEN_WORDS).cpu();
+    }
+    const uint64_t* p = reinterpret_cast<const uint64_t*>(h.data_ptr<int64_t>());
+    return std::vector<uint64_t>(p, p + USTREAM_GEN_WORDS);
+  }
+
+  // n keys in [lo, hi) as an int64 tensor on the stream's device. `slack`
+  // extra words are generated in parallel to cover rejections (< 0: sized
+  // from the rejection rate); too little slack only costs time.
+  torch::Tensor draw(int64_t n, int64_t slack = -1) {
+    TORCH_CHECK(n >= 0, "UniformStream.draw: n must be >= 0");
+    auto opt = torch::TensorOptions().dtype(torch::kInt64).device(dev_);
+    auto out = torch::empty({n}, opt);
+    if (n == 0) return out;
+    if (slack < 0) {
+      double p = (double)thr_ / 4294967296.0;
+      double w0 = (double)n / (1.0 - p);
+      slack = (int64_t)std::ceil(w0 - (double)n + 8.0 * std::sqrt(w0 * p) / (1.0 - p)) + 16;
+    }
+    const int64_t words = n + slack;
+    std::lock_guard<std::mutex> g(mu_);
+    void* st = current_stream(dev_);
+    adopt(st);
+    auto tmp = torch::empty({ustream_tmp_words(words)}, opt);
+    uint64_t* sp = reinterpret_cast<uint64_t*>(state_.data_ptr<int64_t>());
+    if (dev_.is_cuda()) {
+#ifdef ADAPM_WITH_HIP
+      uniform_draw_gpu(sp, lo_, excl_, thr_, n, words, out.data_ptr<int64_t>(),
+                       tmp.data_ptr<int64_t>(), st);
+#else
+      TORCH_CHECK(false, "UniformStream: built without HIP");
+#endif
+    } else {
+      uniform_draw_cpu(sp, lo_, excl_, thr_, n, words, out.data_ptr<int64_t>(),
+                       tmp.data_ptr<int64_t>());
+    }
+    return out;
+  }
+
+  int64_t lo() const { return lo_; }
+  int64_t hi() const { return hi_; }
+  const torch::Device& device() const { return dev_; }
+
+ private:
+  // called with mu_ held
+  void adopt(void* st) {
+#ifdef ADAPM_WITH_HIP
+    if (dev_.is_cuda() && have_owner_ && st != owner_) hipStreamSynchronize((hipStream_t)owner_);
+#endif
+    owner_ = st;
+    have_owner_ = true;
+  }
+
+  int64_t lo_, hi_;
+  uint32_t excl_ = 0, thr_ = 0;
+  torch::Device dev_;
+  torch::Tensor state_;
+  std::mutex mu_;
+  void* owner_ = nullptr;
+  bool have_owner_ = false;
 };
 
 // ---------------------------------------------------------------- server
@@ -2695,27 +2807,95 @@ class Server {
     return false;
   }
 
-  torch::Tensor kge_step_fused(torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o,
-                               torch::Tensor keys_neg, int64_t N, int64_t D, double lr,
-                               double eps) {
+  // Host keys of one fused step, staged with ONE pinned blob (torch's
+  // caching host allocator, as in to_dev) and ONE upload instead of a
+  // pageable, host-blocking copy per array. The upload is a kernel that
+  // reads the pinned blob (copy_keys_gpu says why); the blob is handed back
+  // to the allocator with an event on the stream, so it is not reused
+  // before that kernel has run. The range check rides the copy loop; a bad
+  // key throws before anything is enqueued.
+  struct StagedKeys {
+    torch::Tensor dev;  // keeps the device blob alive
+    std::vector<const int64_t*> ptr;
+  };
+  StagedKeys stage_keys(std::initializer_list<const torch::Tensor*> parts) {
+    int64_t total = 0;
+    for (auto* t : parts) {
+      check_keys(*t);
+      total += t->numel();
+    }
+    auto blob = torch::empty(
+        {total}, torch::TensorOptions().dtype(torch::kInt64).pinned_memory(true));
+    int64_t* dst = blob.data_ptr<int64_t>();
+    const uint64_t lim = (uint64_t)num_keys_;
+    uint64_t bad = 0;
+    for (auto* t : parts) {
+      const int64_t* kp = t->data_ptr<int64_t>();
+      const int64_t n = t->numel();
+      for (int64_t i = 0; i < n; ++i) {
+        int64_t k = kp[i];
+        dst[i] = k;
+        bad |= ((uint64_t)k >= lim);
+      }
+      dst += n;
+    }
+    if (bad)
+      for (auto* t : parts) check_key_range(*t);  // names the offending key
+    StagedKeys sk;
+    sk.dev = torch::empty({total}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
+#ifdef ADAPM_WITH_HIP
+    auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index());
+    TORCH_CHECK(copy_keys_gpu(sk.dev.data_ptr<int64_t>(), blob.data_ptr<int64_t>(), total,
+                              (void*)stream.stream()),
+                "kge_step_fused: the pinned key staging buffer is not visible to the device");
+    at::getHostAllocator(at::kCUDA)->record_event(
+        blob.data_ptr(), blob.storage().data_ptr().get_context(), stream.unwrap());
+#else
+    TORCH_CHECK(false, "kge_step_fused: built without HIP");
+#endif
+    const int64_t* dp = sk.dev.data_ptr<int64_t>();
+    for (auto* t : parts) {
+      sk.ptr.push_back(dp);
+      dp += t->numel();
+    }
+    return sk;
+  }
+
+  // Body shared by kge_step_fused (negatives from the host, staged with the
+  // positives) and kge_step_fused_sampled (negatives drawn on the device
+  // from `us`). Returns the loss and, for the sampled step, the drawn keys.
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_fused_impl(
+      const torch::Tensor& keys_s, const torch::Tensor& keys_r, const torch::Tensor& keys_o,
+      const torch::Tensor* keys_neg, UniformStream* us, int64_t N, int64_t D, double lr,
+      double eps) {
     TORCH_CHECK(world_ == 1, "kge_step_fused requires a single rank (all keys local)");
     TORCH_CHECK(uniform_len_ == 2 * D, "kge_step_fused: store rows must be [emb|accum] = 2D");
     TORCH_CHECK(layout_identity_.load(), "kge_step_fused requires the identity layout");
     TORCH_CHECK(dev_.is_cuda(), "kge_step_fused is the GPU fast path");
-    for (auto* t : {&keys_s, &keys_r, &keys_o, &keys_neg}) check_keys(*t);
     int64_t B = keys_s.numel();
-    TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B && keys_neg.numel() == B * N);
-    auto rng_check = [&](const torch::Tensor& t) { check_key_range(t); };
-    rng_check(keys_s);
-    rng_check(keys_r);
-    rng_check(keys_o);
-    rng_check(keys_neg);
+    TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B);
+    StagedKeys sk;
+    torch::Tensor drawn;
+    const int64_t* kn;
+    if (us) {
+      // device keys never reach the kernel unvalidated: the stream can only
+      // produce keys of [lo, hi), and that range is checked here
+      TORCH_CHECK(us->lo() >= 0 && us->hi() <= num_keys_, "kge_step_fused_sampled: stream range [",
+                  us->lo(), ", ", us->hi(), ") exceeds the store's ", num_keys_, " keys");
+      TORCH_CHECK(us->device() == dev_,
+                  "kge_step_fused_sampled: stream is not on the store's device");
+      TORCH_CHECK(N >= 0 && B * N > 0, "kge_step_fused_sampled: nothing to draw");
+      sk = stage_keys({&keys_s, &keys_r, &keys_o});
+      drawn = us->draw(B * N);
+      kn = drawn.data_ptr<int64_t>();
+    } else {
+      TORCH_CHECK(keys_neg->numel() == B * N);
+      sk = stage_keys({&keys_s, &keys_r, &keys_o, keys_neg});
+      kn = sk.ptr[3];
+    }
+    const int64_t *ks = sk.ptr[0], *kr = sk.ptr[1], *ko = sk.ptr[2];
 
     auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    auto ks = keys_s.to(dev_, true);
-    auto kr = keys_r.to(dev_, true);
-    auto ko = keys_o.to(dev_, true);
-    auto kn = keys_neg.to(dev_, true);
     void* st = current_stream(dev_);
     {
       InflightGuard g(this);
@@ -2728,10 +2908,7 @@ class Server {
       if (fused_plain_ok(st)) {
         // pre-pass, step and clean-up are enqueued under the lock: the row
         // marks are per server, and a second caller must find them zeroed
-        RowMarkKeys mk{{ks.data_ptr<int64_t>(), kr.data_ptr<int64_t>(), ko.data_ptr<int64_t>(),
-                        kn.data_ptr<int64_t>()},
-                       {B, B, B, B * N},
-                       4};
+        RowMarkKeys mk{{ks, kr, ko, kn}, {B, B, B, B * N}, 4};
         auto* marks = reinterpret_cast<uint32_t*>(fused_marks_.data_ptr<int32_t>());
         rowmark_set_gpu(marks, mk, st);
         kge_complex_step_fused_gpu(
@@ -2745,11 +2922,9 @@ class Server {
         stat_fused_plain_ += 1;
       } else {
         mg.unlock();
-        kge_complex_step_fused_gpu(slab_.data, ks.data_ptr<int64_t>(), kr.data_ptr<int64_t>(),
-                                   ko.data_ptr<int64_t>(), kn.data_ptr<int64_t>(),
-                                   loss.data_ptr<float>(), (int)B, (int)N, (int)D,
-                                   Slab::padded(uniform_len_), world_, rank_, (float)lr,
-                                   (float)eps, st);
+        kge_complex_step_fused_gpu(slab_.data, ks, kr, ko, kn, loss.data_ptr<float>(), (int)B,
+                                   (int)N, (int)D, Slab::padded(uniform_len_), world_, rank_,
+                                   (float)lr, (float)eps, st);
         stat_fused_atomic_ += 1;
       }
     }
@@ -2760,7 +2935,23 @@ class Server {
     stat_push_local_ += total;
     stat_pulls_ += 1;
     stat_pushes_ += 1;
-    return loss;
+    return {loss, drawn};
+  }
+
+  torch::Tensor kge_step_fused(torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o,
+                               torch::Tensor keys_neg, int64_t N, int64_t D, double lr,
+                               double eps) {
+    return std::get<0>(
+        kge_step_fused_impl(keys_s, keys_r, keys_o, &keys_neg, nullptr, N, D, lr, eps));
+  }
+
+  // The same step with its B*N negatives drawn on the device from `us`
+  // (numpy-exact, see UniformStream): no host draw, no 8*B*N-byte upload, no
+  // host scan of the negatives. Returns (loss, negative keys on the device).
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_fused_sampled(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, UniformStream& us,
+      int64_t N, int64_t D, double lr, double eps) {
+    return kge_step_fused_impl(keys_s, keys_r, keys_o, nullptr, &us, N, D, lr, eps);
   }
 
   // ---- fused slab-direct steps at world>1 / relocated layouts --------
@@ -3781,6 +3972,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w2v_sgns_step", &w2v_sgns_step, py::call_guard<py::gil_scoped_release>());
   m.def("mf_update_step", &mf_update_step, py::call_guard<py::gil_scoped_release>());
   m.def("mf_loss", &mf_loss, py::call_guard<py::gil_scoped_release>());
+  py::class_<UniformStream>(m, "UniformStream")
+      .def(py::init<int64_t, int64_t, std::string>(), py::arg("lo"), py::arg("hi"),
+           py::arg("device"))
+      .def_static("supported", &UniformStream::supported)
+      .def("import_state", &UniformStream::import_state, py::call_guard<py::gil_scoped_release>())
+      .def("export_state", &UniformStream::export_state, py::call_guard<py::gil_scoped_release>())
+      .def("draw", &UniformStream::draw, py::arg("n"), py::arg("slack") = -1,
+           py::call_guard<py::gil_scoped_release>())
+      .def("lo", &UniformStream::lo)
+      .def("hi", &UniformStream::hi);
   py::class_<Server>(m, "Server")
       .def(py::init<int64_t, torch::Tensor, int, int, int, int, std::string, double, int, bool,
                     int64_t, int64_t, double>(),
@@ -3815,6 +4016,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("failed_reason", &Server::failed_reason)
       .def("scan_local", &Server::scan_local, py::call_guard<py::gil_scoped_release>())
       .def("kge_step_fused", &Server::kge_step_fused, py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_fused_sampled", &Server::kge_step_fused_sampled,
+           py::call_guard<py::gil_scoped_release>())
       .def("w2v_step_fused", &Server::w2v_step_fused, py::call_guard<py::gil_scoped_release>())
       .def("mf_step_fused", &Server::mf_step_fused, py::call_guard<py::gil_scoped_release>())
       .def("kge_step_fused_general", &Server::kge_step_fused_general,

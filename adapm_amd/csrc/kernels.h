@@ -151,6 +151,28 @@ void alias_draw_gpu(const float* prob, const int32_t* alias, int64_t n, uint64_t
 void alias_draw_cpu(const float* prob, const int32_t* alias, int64_t n, uint64_t seed,
                     int64_t N, int64_t* out);
 
+// Uniform key draw that continues numpy's PCG64 bounded-integer stream bit
+// for bit (ustream.h has the model). `state` is USTREAM_STATE_WORDS uint64
+// words, `tmp` scratch of ustream_tmp_words(words) int64, both on the op
+// device; `words` >= n is how many stream words are generated in parallel
+// before compaction. Writes out[0..n) and leaves `state` where numpy would
+// have left it. If fewer than n of the `words` are accepted, the last step
+// continues the stream sequentially, so the result never depends on the
+// slack. The device draw is two launches on `stream` and never
+// synchronises; the CPU twin runs the same chunked jump-ahead and
+// compaction in loops.
+void uniform_draw_gpu(uint64_t* state, int64_t lo, uint32_t excl, uint32_t thr, int64_t n,
+                      int64_t words, int64_t* out, int64_t* tmp, void* stream);
+void uniform_draw_cpu(uint64_t* state, int64_t lo, uint32_t excl, uint32_t thr, int64_t n,
+                      int64_t words, int64_t* out, int64_t* tmp);
+
+// dst[0..n) (device) = src_host[0..n) (pinned, device-visible host memory),
+// as a kernel on `stream`: for a few hundred KB of keys per step this keeps
+// the upload in the compute queue, where a copy-engine transfer between two
+// kernels costs a queue hand-over on either side. Returns false, with
+// nothing enqueued, if src_host is not device-visible.
+bool copy_keys_gpu(int64_t* dst, const int64_t* src_host, int64_t n, void* stream);
+
 }  // namespace adapm
 
 namespace adapm {

@@ -1,10 +1,12 @@
 // CPU backend of the app kernels (kernels.h) — identical math to
 // kernels_hip.hip, used by the no-GPU test tier and as the reference for
 // GPU numerics tests (alongside plain-torch fp32 references in tests/).
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "kernels.h"
+#include "ustream.h"
 
 namespace adapm {
 
@@ -292,6 +294,34 @@ void alias_draw_cpu(const float* prob, const int32_t* alias, int64_t n, uint64_t
     float u = (float)((h >> 40) & 0xffffff) * (1.0f / 16777216.0f);
     out[i] = (u < prob[slot]) ? slot : (int64_t)alias[slot];
   }
+}
+
+// CPU twin of uniform_draw_gpu: the same per-chunk jump-ahead, the same
+// scratch (keys in word order here, thread-interleaved on the device), and
+// a compaction over the per-block counts.
+void uniform_draw_cpu(uint64_t* state, int64_t lo, uint32_t excl, uint32_t thr, int64_t n,
+                      int64_t words, int64_t* out, int64_t* tmp) {
+  const UStreamRange r{lo, excl, thr};
+  const int64_t chunks = ustream_chunks(words), nb = ustream_blocks(words);
+  int64_t* counts = tmp + USTREAM_TMP_COUNTS;
+  int64_t* keys = counts + nb;
+  for (int64_t b = 0; b < nb; ++b) counts[b] = 0;
+  for (int64_t c = 0; c < chunks; ++c)
+    counts[c / USTREAM_BLOCK] +=
+        ustream_gen_chunk(state, r, words, c, keys + c * USTREAM_CHUNK, 1);
+  int64_t total = 0, consumed = 0;
+  for (int64_t b = 0; b < nb; ++b) {
+    int64_t idx = total;  // block offset = sum of the counts before it
+    total += counts[b];
+    if (idx >= n) continue;
+    const int64_t w1 = std::min((b + 1) * (int64_t)USTREAM_BLOCK * USTREAM_CHUNK, words);
+    for (int64_t w = b * (int64_t)USTREAM_BLOCK * USTREAM_CHUNK; w < w1 && idx < n; ++w) {
+      if (keys[w] == USTREAM_REJECTED) continue;
+      out[idx++] = keys[w];
+      if (idx == n) consumed = w + 1;
+    }
+  }
+  ustream_finish(state, r, n, words, total, consumed, out);
 }
 
 }  // namespace adapm

@@ -9,6 +9,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "ustream.h"
 
 namespace adapm {
 
@@ -372,6 +373,133 @@ void alias_draw_gpu(const float* prob, const int32_t* alias, int64_t n, uint64_t
   int blocks = (int)std::min<int64_t>((N + 255) / 256, 4096);
   hipLaunchKernelGGL(k_alias_draw, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prob, alias,
                      n, seed, N, out);
+}
+}  // namespace adapm
+
+// --------------------------------------------------------------- uniform draw
+//
+// numpy-exact uniform keys (ustream.h) in two launches: generate + flag,
+// then compact. The state is written back by the one thread of the second
+// launch that can: the thread that writes key n-1 knows how many words were
+// consumed; if the words fall short of n keys nobody writes key n-1, and
+// thread 0 of the last workgroup, which has the total, continues the
+// stream. Either needs nothing from another workgroup of its launch, so
+// there is no fence and no third launch. One thread per chunk of USTREAM_CHUNK
+// words, USTREAM_BLOCK chunks per workgroup; the scratch keys of a
+// workgroup are interleaved by thread (word i of thread t at i*KT + t), so
+// both launches touch them with coalesced accesses. The 2 MB of scratch at
+// the benchmark's 262,144 draws stay in L2 between the launches.
+namespace adapm {
+
+static_assert(USTREAM_BLOCK == KT, "one chunk per thread of a KT workgroup");
+
+__device__ inline int64_t block_reduce_i64(int64_t v, int64_t* lds) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int64_t out = 0;
+  for (int i = 0; i < KT / 64; ++i) out += lds[i];
+  __syncthreads();
+  return out;
+}
+
+template <typename T>
+__device__ inline T* ustream_block_keys(T* tmp, int64_t nb, int64_t block) {
+  return tmp + USTREAM_TMP_COUNTS + nb + block * (KT * USTREAM_CHUNK) + threadIdx.x;
+}
+
+__global__ void __launch_bounds__(KT)
+k_ustream_gen(const uint64_t* __restrict__ state, UStreamRange r, int64_t words, int64_t chunks,
+              int64_t* __restrict__ tmp, int64_t nb) {
+  __shared__ int64_t lds[KT / 64];
+  const int64_t c = (int64_t)blockIdx.x * KT + threadIdx.x;
+  int64_t cnt = 0;
+  if (c < chunks)
+    cnt = ustream_gen_chunk(state, r, words, c, ustream_block_keys(tmp, nb, blockIdx.x), KT);
+  cnt = block_reduce_i64(cnt, lds);
+  if (threadIdx.x == 0) {
+    tmp[USTREAM_TMP_COUNTS + blockIdx.x] = cnt;
+  }
+}
+
+__global__ void __launch_bounds__(KT)
+k_ustream_compact(uint64_t* __restrict__ state, UStreamRange r, int64_t n, int64_t words,
+                  int64_t chunks, const int64_t* __restrict__ tmp, int64_t nb,
+                  int64_t* __restrict__ out) {
+  __shared__ int64_t lds[KT / 64];
+  __shared__ int wave_tot[KT / 64];
+  const int64_t* counts = tmp + USTREAM_TMP_COUNTS;
+  int64_t part = 0;
+  for (int64_t i = threadIdx.x; i < (int64_t)blockIdx.x; i += KT) part += counts[i];
+  const int64_t off = block_reduce_i64(part, lds);
+  const int64_t c = (int64_t)blockIdx.x * KT + threadIdx.x;
+  const bool live = off < n && c < chunks;  // off is uniform over the workgroup
+  const int64_t* kc = ustream_block_keys(tmp, nb, blockIdx.x);
+  int64_t k[USTREAM_CHUNK];
+  int cnt = 0;
+#pragma unroll
+  for (int i = 0; i < USTREAM_CHUNK; ++i) {
+    k[i] = live ? kc[i * KT] : USTREAM_REJECTED;
+    cnt += (k[i] != USTREAM_REJECTED);
+  }
+  // exclusive scan of cnt over the workgroup
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = cnt;
+  for (int d = 1; d < 64; d <<= 1) {
+    int y = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += y;
+  }
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  int64_t idx = off + incl - cnt;
+  for (int i = 0; i < wave; ++i) idx += wave_tot[i];
+  int64_t consumed = 0;
+#pragma unroll
+  for (int i = 0; i < USTREAM_CHUNK; ++i) {
+    if (k[i] == USTREAM_REJECTED) continue;
+    if (idx < n) {
+      out[idx] = k[i];
+      if (idx == n - 1) consumed = c * USTREAM_CHUNK + i + 1;
+    }
+    ++idx;
+  }
+  if (consumed) {
+    ustream_finish(state, r, n, words, n, consumed, out);
+  } else if (blockIdx.x == nb - 1 && threadIdx.x == 0) {
+    int64_t total = off;
+    for (int i = 0; i < KT / 64; ++i) total += wave_tot[i];
+    if (total < n) ustream_finish(state, r, n, words, total, 0, out);
+  }
+}
+
+void uniform_draw_gpu(uint64_t* state, int64_t lo, uint32_t excl, uint32_t thr, int64_t n,
+                      int64_t words, int64_t* out, int64_t* tmp, void* stream) {
+  if (n <= 0) return;
+  const UStreamRange r{lo, excl, thr};
+  const int64_t chunks = ustream_chunks(words), nb = ustream_blocks(words);
+  auto st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_ustream_gen, dim3((unsigned)nb), dim3(KT), 0, st, state, r, words, chunks,
+                     tmp, nb);
+  hipLaunchKernelGGL(k_ustream_compact, dim3((unsigned)nb), dim3(KT), 0, st, state, r, n, words,
+                     chunks, tmp, nb, out);
+}
+
+__global__ void k_copy_keys(int64_t* __restrict__ dst, const int64_t* __restrict__ src,
+                            int64_t n) {
+  int64_t i = (int64_t)blockIdx.x * KT + threadIdx.x;
+  if (i < n) dst[i] = src[i];
+}
+
+bool copy_keys_gpu(int64_t* dst, const int64_t* src_host, int64_t n, void* stream) {
+  if (n <= 0) return true;
+  void* src = nullptr;  // fails for memory the device cannot read
+  if (hipHostGetDevicePointer(&src, const_cast<int64_t*>(src_host), 0) != hipSuccess || !src) {
+    (void)hipGetLastError();
+    return false;
+  }
+  hipLaunchKernelGGL(k_copy_keys, dim3((unsigned)((n + KT - 1) / KT)), dim3(KT), 0,
+                     (hipStream_t)stream, dst, static_cast<const int64_t*>(src), n);
+  return true;
 }
 }  // namespace adapm
 

@@ -26,6 +26,8 @@ import numpy as np
 import torch
 
 _PHASE_TIMING = os.environ.get("ADAPM_PHASE_TIMING", "0") == "1"
+# A/B switch: keep the host draw of the negatives on the fused world==1 path
+_HOST_NEGATIVES = os.environ.get("ADAPM_HOST_NEGATIVES", "0") == "1"
 
 import adapm_amd
 from adapm_amd import _C
@@ -189,9 +191,25 @@ class ComplEx:
             return self.train_batch(triples, sync_loss=sync_loss)
         B = len(triples)
         s_keys, r_keys, o_keys = self.keys_of(triples)
+
+        fast = self.world == 1 and not force_general and raw.layout_identity()
+        smp = self.server.sampling
+        if fast and smp is not None and not _HOST_NEGATIVES and smp.device_stream() is not None:
+            # negatives drawn on the device inside the step: the same keys
+            # the host draw would give (ADAPM_HOST_NEGATIVES=1 keeps that
+            # draw, for A/B runs)
+            NN = B * cfg.neg_samples
+            sid = w.prepare_sample(NN, w.current_clock(), w.current_clock() + 2)
+            us = smp.pull_device(w, sid, NN, draw=False)
+            w.finish_sample(sid)
+            loss, _neg = raw.kge_step_fused_sampled(
+                torch.from_numpy(s_keys), torch.from_numpy(r_keys), torch.from_numpy(o_keys),
+                us, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
+            return float(loss.mean().item()) if sync_loss else loss
+
         neg_keys = np.ascontiguousarray(self._draw_negatives(B), dtype=np.int64)
 
-        if self.world == 1 and not force_general and raw.layout_identity():
+        if fast:
             loss = raw.kge_step_fused(
                 torch.from_numpy(s_keys), torch.from_numpy(r_keys), torch.from_numpy(o_keys),
                 torch.from_numpy(neg_keys), cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)

@@ -5,7 +5,9 @@ uniform / log-uniform distributions of the reference bindings
 
 Keys are drawn host-side (keys route on the host anyway); the Local
 scheme's locality scan runs in C++ over the store's presence metadata
-(Server.scan_local)."""
+(Server.scan_local). The one exception is the device pull of uniform keys
+at world == 1 (SamplingManager.device_stream / pull_device), which gives
+the host draw's keys bit for bit."""
 from __future__ import annotations
 
 import threading
@@ -21,13 +23,85 @@ class Distribution:
         raise NotImplementedError
 
 
+_M64 = (1 << 64) - 1
+
+
 class Uniform(Distribution):
+    """Uniform keys in [lo, hi). One stream, two sides: the numpy generator
+    serves draw(); the native stream (_C.UniformStream, on the store's
+    device or the CPU twin) serves draw_native() and continues the same
+    PCG64 stream bit for bit, so the key sequence does not depend on which
+    side serves which call. Whichever side drew last holds the state; it is
+    moved across on the next call to the other side (device -> host is one
+    small blocking copy)."""
+
     def __init__(self, lo: int, hi: int, seed: int):
         self.lo, self.hi = lo, hi
         self.rng = np.random.default_rng(seed)
+        self._native = None
+        self._native_dev = None
+        self._native_live = False  # the native side holds the current state
+        self._mu = threading.Lock()
 
     def draw(self, n):
-        return self.rng.integers(self.lo, self.hi, size=n, dtype=np.int64)
+        with self._mu:
+            self._to_host()
+            return self.rng.integers(self.lo, self.hi, size=n, dtype=np.int64)
+
+    # ------------------------------------------------ native side
+
+    def native_supported(self) -> bool:
+        """Ranges of numpy's 32-bit bounded draw; everything else (one
+        value, exactly 2**32 values, wider) stays on the host."""
+        from . import _C
+
+        if type(self.rng.bit_generator).__name__ != "PCG64":
+            return False
+        if not (-(1 << 63) <= self.lo and self.hi <= (1 << 63) - 1):
+            return False
+        return _C.UniformStream.supported(self.lo, self.hi)
+
+    def native_stream(self, device="cpu"):
+        """The native stream on `device`, holding the current state (the
+        device side is authoritative until the next host draw)."""
+        with self._mu:
+            return self._to_native(str(device))
+
+    def draw_native(self, n: int, device="cpu", slack: int = -1):
+        """n keys as an int64 tensor on `device`, or a host draw (as a CPU
+        tensor) where the native path does not cover the range."""
+        if not self.native_supported():
+            return torch.from_numpy(self.draw(n))
+        with self._mu:
+            return self._to_native(str(device)).draw(n, slack)
+
+    def _to_native(self, device: str):
+        from . import _C
+
+        if self._native is not None and self._native_dev != device:
+            self._to_host()
+            self._native = None
+        if self._native is None:
+            self._native = _C.UniformStream(self.lo, self.hi, device)
+            self._native_dev = device
+        if not self._native_live:
+            st = self.rng.bit_generator.state
+            s, inc = st["state"]["state"], st["state"]["inc"]
+            self._native.import_state(s >> 64, s & _M64, inc >> 64, inc & _M64,
+                                      int(st["has_uint32"]), int(st["uinteger"]))
+            self._native_live = True
+        return self._native
+
+    def _to_host(self):
+        if not self._native_live:
+            return
+        w = self._native.export_state()
+        st = self.rng.bit_generator.state
+        st["state"] = {"state": (w[0] << 64) | w[1], "inc": (w[2] << 64) | w[3]}
+        st["has_uint32"] = int(w[4])
+        st["uinteger"] = int(w[5])
+        self.rng.bit_generator.state = st
+        self._native_live = False
 
 
 class LogUniform(Distribution):
@@ -102,7 +176,8 @@ class SamplingManager:
     keeps it on the server; sample ids are (wid, counter))."""
 
     def __init__(self, server, scheme: str, with_replacement: bool, dist_: Distribution,
-                 lo: int, hi: int, pool_size: int = 5_000, reuse_factor: int = 4):
+                 lo: int, hi: int, pool_size: int = 5_000, reuse_factor: int = 4,
+                 device=None):
         self.POOL_SIZE = pool_size    # reference --sampling.pool_size
         self.POOL_REUSE = reuse_factor  # reference --sampling.reuse_factor
         self.server = server
@@ -110,6 +185,7 @@ class SamplingManager:
         self.with_replacement = with_replacement
         self.dist = dist_
         self.lo, self.hi = lo, hi
+        self.device = None if device is None else str(device)
         self.lock = threading.Lock()
         self.samples: Dict[int, _Sample] = {}
         self.next_id = 1
@@ -150,6 +226,33 @@ class SamplingManager:
 
     def finish(self, sid: int):
         self.samples.pop(sid, None)
+
+    def device_stream(self):
+        """The native uniform stream on the store's device when negatives
+        can be drawn there with the host draw's exact result: local scheme
+        at world == 1 (every key is local, no scan), with replacement,
+        Uniform over a range the native draw covers, GPU store. None
+        otherwise — the caller stays on pull()."""
+        if (self.scheme != "local" or not self.with_replacement
+                or self.server.world() != 1 or not isinstance(self.dist, Uniform)
+                or self.device is None or not self.device.startswith("cuda")
+                or not self.dist.native_supported()):
+            return None
+        return self.dist.native_stream(self.device)
+
+    def pull_device(self, worker, sid: int, n: int, draw: bool = True):
+        """Device pull of sample `sid`: the same bookkeeping as pull(), the
+        keys drawn on the store's device (an int64 device tensor). With
+        draw=False only the bookkeeping is done and the native stream is
+        returned, for a fused step that draws the keys itself."""
+        us = self.device_stream()
+        if us is None:
+            raise RuntimeError("device pull is not available for this sampling setup")
+        s = self.samples[sid]
+        if s.remaining < n:
+            raise ValueError(f"sample {sid}: requested {n} > remaining {s.remaining}")
+        s.remaining -= n
+        return us.draw(n) if draw else us
 
     # ------------------------------------------------ internals
 

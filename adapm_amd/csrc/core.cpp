@@ -80,6 +80,13 @@ static void* current_stream(const torch::Device& dev) {
   return nullptr;
 }
 
+// GPU ComplEx / SGNS steps keep a row in registers (STEP_MAX_LANES,
+// kernels.h): refuse a longer row before anything is enqueued.
+static void check_step_lanes(const char* name, const char* what, int64_t lanes) {
+  TORCH_CHECK(lanes <= STEP_MAX_LANES, name, ": ", what, " = ", lanes,
+              " exceeds the GPU step kernels' limit of ", STEP_MAX_LANES);
+}
+
 // ---------------------------------------------------------------- slab
 
 // Flat float32 value arena with size-class free lists. Slot sizes are
@@ -2807,6 +2814,26 @@ class Server {
     return false;
   }
 
+  // What every identity-path fused step needs: key k lives at row k of a
+  // GPU slab whose rows are [emb(D) | accum(D)].
+  void check_fused_identity(const char* name, int64_t D) {
+    TORCH_CHECK(world_ == 1, name, " requires a single rank (all keys local)");
+    TORCH_CHECK(uniform_len_ == 2 * D, name, ": store rows must be [emb|accum] = 2D");
+    TORCH_CHECK(layout_identity_.load(), name, " requires the identity layout");
+    TORCH_CHECK(dev_.is_cuda(), name, " is the GPU fast path");
+  }
+
+  // A fused step reads and updates the store once per key: one pull and one
+  // push of `keys` local keys in the stats.
+  void count_fused_ops(int64_t keys) {
+    stat_pull_keys_ += keys;
+    stat_pull_local_ += keys;
+    stat_push_keys_ += keys;
+    stat_push_local_ += keys;
+    stat_pulls_ += 1;
+    stat_pushes_ += 1;
+  }
+
   // Host keys of one fused step, staged with ONE pinned blob (torch's
   // caching host allocator, as in to_dev) and ONE upload instead of a
   // pageable, host-blocking copy per array. The upload is a kernel that
@@ -2818,7 +2845,7 @@ class Server {
     torch::Tensor dev;  // keeps the device blob alive
     std::vector<const int64_t*> ptr;
   };
-  StagedKeys stage_keys(std::initializer_list<const torch::Tensor*> parts) {
+  StagedKeys stage_keys(const char* name, std::initializer_list<const torch::Tensor*> parts) {
     int64_t total = 0;
     for (auto* t : parts) {
       check_keys(*t);
@@ -2847,11 +2874,11 @@ class Server {
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index());
     TORCH_CHECK(copy_keys_gpu(sk.dev.data_ptr<int64_t>(), blob.data_ptr<int64_t>(), total,
                               (void*)stream.stream()),
-                "kge_step_fused: the pinned key staging buffer is not visible to the device");
+                name, ": the pinned key staging buffer is not visible to the device");
     at::getHostAllocator(at::kCUDA)->record_event(
         blob.data_ptr(), blob.storage().data_ptr().get_context(), stream.unwrap());
 #else
-    TORCH_CHECK(false, "kge_step_fused: built without HIP");
+    TORCH_CHECK(false, name, ": built without HIP");
 #endif
     const int64_t* dp = sk.dev.data_ptr<int64_t>();
     for (auto* t : parts) {
@@ -2868,10 +2895,8 @@ class Server {
       const torch::Tensor& keys_s, const torch::Tensor& keys_r, const torch::Tensor& keys_o,
       const torch::Tensor* keys_neg, UniformStream* us, int64_t N, int64_t D, double lr,
       double eps) {
-    TORCH_CHECK(world_ == 1, "kge_step_fused requires a single rank (all keys local)");
-    TORCH_CHECK(uniform_len_ == 2 * D, "kge_step_fused: store rows must be [emb|accum] = 2D");
-    TORCH_CHECK(layout_identity_.load(), "kge_step_fused requires the identity layout");
-    TORCH_CHECK(dev_.is_cuda(), "kge_step_fused is the GPU fast path");
+    check_fused_identity("kge_step_fused", D);
+    check_step_lanes("kge_step_fused", "D/2", D / 2);
     int64_t B = keys_s.numel();
     TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B);
     StagedKeys sk;
@@ -2885,12 +2910,12 @@ class Server {
       TORCH_CHECK(us->device() == dev_,
                   "kge_step_fused_sampled: stream is not on the store's device");
       TORCH_CHECK(N >= 0 && B * N > 0, "kge_step_fused_sampled: nothing to draw");
-      sk = stage_keys({&keys_s, &keys_r, &keys_o});
+      sk = stage_keys("kge_step_fused", {&keys_s, &keys_r, &keys_o});
       drawn = us->draw(B * N);
       kn = drawn.data_ptr<int64_t>();
     } else {
       TORCH_CHECK(keys_neg->numel() == B * N);
-      sk = stage_keys({&keys_s, &keys_r, &keys_o, keys_neg});
+      sk = stage_keys("kge_step_fused", {&keys_s, &keys_r, &keys_o, keys_neg});
       kn = sk.ptr[3];
     }
     const int64_t *ks = sk.ptr[0], *kr = sk.ptr[1], *ko = sk.ptr[2];
@@ -2913,8 +2938,8 @@ class Server {
         rowmark_set_gpu(marks, mk, st);
         kge_complex_step_fused_gpu(
             slab_.data, mk.keys[0], mk.keys[1], mk.keys[2], mk.keys[3], loss.data_ptr<float>(),
-            (int)B, (int)N, (int)D, Slab::padded(uniform_len_), world_, rank_, (float)lr,
-            (float)eps, st, marks,
+            (int)B, (int)N, (int)D, Slab::padded(uniform_len_), world_, (float)lr, (float)eps,
+            st, marks,
             fused_shared_stat_.defined()
                 ? reinterpret_cast<unsigned long long*>(fused_shared_stat_.data_ptr<int64_t>())
                 : nullptr);
@@ -2923,18 +2948,12 @@ class Server {
       } else {
         mg.unlock();
         kge_complex_step_fused_gpu(slab_.data, ks, kr, ko, kn, loss.data_ptr<float>(), (int)B,
-                                   (int)N, (int)D, Slab::padded(uniform_len_), world_, rank_,
-                                   (float)lr, (float)eps, st);
+                                   (int)N, (int)D, Slab::padded(uniform_len_), world_, (float)lr,
+                                   (float)eps, st);
         stat_fused_atomic_ += 1;
       }
     }
-    int64_t total = 3 * B + B * N;
-    stat_pull_keys_ += total;
-    stat_pull_local_ += total;
-    stat_push_keys_ += total;
-    stat_push_local_ += total;
-    stat_pulls_ += 1;
-    stat_pushes_ += 1;
+    count_fused_ops(3 * B + B * N);
     return {loss, drawn};
   }
 
@@ -2972,6 +2991,10 @@ class Server {
     std::vector<std::vector<int64_t>> offs;  // per input array, compacted
     std::vector<int64_t> missed;             // sample indices (ascending)
     int64_t b_hit = 0;
+    // offs where the step reads them, filled by step_fused_general: the
+    // host vectors on a CPU store, device copies (kept alive here) on a GPU
+    std::vector<const int64_t*> ptr;
+    std::vector<torch::Tensor> dev;
   };
 
   FusedResolve resolve_fused(const std::vector<std::pair<const int64_t*, int>>& arrs,
@@ -3052,105 +3075,85 @@ class Server {
     return dev_.is_cuda() ? t.to(dev_, /*non_blocking=*/true) : t;
   }
 
-  std::tuple<torch::Tensor, torch::Tensor> kge_step_fused_general(
-      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, torch::Tensor keys_neg,
-      int64_t N, int64_t D, double lr, double eps) {
+  // Skeleton of every *_step_fused_general entry. `arrs` are the key arrays
+  // with their keys per sample (the first has one); `step(res, loss)` runs
+  // the model's step over the res.b_hit compacted samples at res.ptr.
+  // Returns (loss of the hit samples, indices of the missed ones).
+  using FusedKeyArrays = std::initializer_list<std::pair<const torch::Tensor*, int64_t>>;
+  template <typename Step>
+  std::tuple<torch::Tensor, torch::Tensor> step_fused_general(const char* name,
+                                                              FusedKeyArrays arrs, Step&& step) {
     check_not_failed();
-    TORCH_CHECK(uniform_len_ == 2 * D, "kge_step_fused: store rows must be [emb|accum] = 2D");
-    for (auto* t : {&keys_s, &keys_r, &keys_o, &keys_neg}) {
-      check_keys(*t);
-      check_key_range(*t);
+    const int64_t B = arrs.begin()->first->numel();
+    std::vector<std::pair<const int64_t*, int>> raw;
+    int64_t per_sample = 0;
+    for (auto& a : arrs) {
+      check_keys(*a.first);
+      check_key_range(*a.first);
+      TORCH_CHECK(a.first->numel() == B * a.second, name, ": key arrays disagree on the batch");
+      raw.emplace_back(a.first->data_ptr<int64_t>(), (int)a.second);
+      per_sample += a.second;
     }
-    int64_t B = keys_s.numel();
-    TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B && keys_neg.numel() == B * N);
-
     torch::Tensor loss, missed_t;
     {
       InflightGuard g(this);
-      auto res = resolve_fused({{keys_s.data_ptr<int64_t>(), 1},
-                                {keys_r.data_ptr<int64_t>(), 1},
-                                {keys_o.data_ptr<int64_t>(), 1},
-                                {keys_neg.data_ptr<int64_t>(), (int)N}},
-                               B);
-      int64_t Bh = res.b_hit;
-      loss = torch::empty({Bh}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-      if (Bh > 0) {
-        if (dev_.is_cuda()) {
-          auto os = offs_to_dev(res.offs[0]);
-          auto orr = offs_to_dev(res.offs[1]);
-          auto oo = offs_to_dev(res.offs[2]);
-          auto on = offs_to_dev(res.offs[3]);
-          kge_complex_step_fused_gpu(slab_.data, os.data_ptr<int64_t>(), orr.data_ptr<int64_t>(),
-                                     oo.data_ptr<int64_t>(), on.data_ptr<int64_t>(),
-                                     loss.data_ptr<float>(), (int)Bh, (int)N, (int)D,
-                                     Slab::padded(uniform_len_), /*world=offsets-mode*/ 0, rank_,
-                                     (float)lr, (float)eps, current_stream(dev_));
-        } else {
-          std::lock_guard<std::mutex> vg(cpu_val_mu_);
-          kge_complex_step_fused_offs_cpu(slab_.data, res.offs[0].data(), res.offs[1].data(),
-                                          res.offs[2].data(), res.offs[3].data(),
-                                          loss.data_ptr<float>(), (int)Bh, (int)N, (int)D,
-                                          (float)lr, (float)eps);
+      auto res = resolve_fused(raw, B);
+      loss = torch::empty({res.b_hit}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+      if (res.b_hit > 0) {
+        for (auto& o : res.offs) {
+          if (dev_.is_cuda()) res.dev.push_back(offs_to_dev(o));
+          res.ptr.push_back(dev_.is_cuda() ? res.dev.back().data_ptr<int64_t>() : o.data());
         }
+        step(res, loss.data_ptr<float>());
       }
       missed_t = i64vec_to_tensor(res.missed);
-      int64_t total = (3 + N) * Bh;
-      stat_pull_keys_ += total;
-      stat_pull_local_ += total;
-      stat_push_keys_ += total;
-      stat_push_local_ += total;
-      stat_pulls_ += 1;
-      stat_pushes_ += 1;
+      count_fused_ops(per_sample * res.b_hit);
     }
     return {loss, missed_t};
+  }
+
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_fused_general(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, torch::Tensor keys_neg,
+      int64_t N, int64_t D, double lr, double eps) {
+    TORCH_CHECK(uniform_len_ == 2 * D, "kge_step_fused: store rows must be [emb|accum] = 2D");
+    if (dev_.is_cuda()) check_step_lanes("kge_step_fused", "D/2", D / 2);
+    return step_fused_general(
+        "kge_step_fused", {{&keys_s, 1}, {&keys_r, 1}, {&keys_o, 1}, {&keys_neg, N}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          if (dev_.is_cuda()) {
+            kge_complex_step_fused_gpu(slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], res.ptr[3],
+                                       loss, Bh, (int)N, (int)D, Slab::padded(uniform_len_),
+                                       /*world=offsets-mode*/ 0, (float)lr, (float)eps,
+                                       current_stream(dev_));
+          } else {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            kge_complex_step_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[1], res.ptr[2],
+                                            res.ptr[3], loss, Bh, (int)N, (int)D, (float)lr,
+                                            (float)eps);
+          }
+        });
   }
 
   std::tuple<torch::Tensor, torch::Tensor> w2v_step_fused_general(
       torch::Tensor keys_ctr, torch::Tensor keys_ctx, torch::Tensor keys_neg, int64_t N,
       int64_t D, double lr, double eps) {
-    check_not_failed();
     TORCH_CHECK(uniform_len_ == 2 * D, "w2v_step_fused: store rows must be [emb|accum] = 2D");
-    for (auto* t : {&keys_ctr, &keys_ctx, &keys_neg}) {
-      check_keys(*t);
-      check_key_range(*t);
-    }
-    int64_t B = keys_ctr.numel();
-    TORCH_CHECK(keys_ctx.numel() == B && keys_neg.numel() == B * N);
-    torch::Tensor loss, missed_t;
-    {
-      InflightGuard g(this);
-      auto res = resolve_fused({{keys_ctr.data_ptr<int64_t>(), 1},
-                                {keys_ctx.data_ptr<int64_t>(), 1},
-                                {keys_neg.data_ptr<int64_t>(), (int)N}},
-                               B);
-      int64_t Bh = res.b_hit;
-      loss = torch::empty({Bh}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-      if (Bh > 0) {
-        if (dev_.is_cuda()) {
-          auto oc = offs_to_dev(res.offs[0]);
-          auto ox = offs_to_dev(res.offs[1]);
-          auto on = offs_to_dev(res.offs[2]);
-          w2v_sgns_step_fused_gpu(slab_.data, oc.data_ptr<int64_t>(), ox.data_ptr<int64_t>(),
-                                  on.data_ptr<int64_t>(), loss.data_ptr<float>(), (int)Bh,
-                                  (int)N, (int)D, Slab::padded(uniform_len_), 0, (float)lr,
-                                  (float)eps, current_stream(dev_));
-        } else {
-          std::lock_guard<std::mutex> vg(cpu_val_mu_);
-          w2v_sgns_step_fused_offs_cpu(slab_.data, res.offs[0].data(), res.offs[1].data(),
-                                       res.offs[2].data(), loss.data_ptr<float>(), (int)Bh,
-                                       (int)N, (int)D, (float)lr, (float)eps);
-        }
-      }
-      missed_t = i64vec_to_tensor(res.missed);
-      int64_t total = (2 + N) * Bh;
-      stat_pull_keys_ += total;
-      stat_pull_local_ += total;
-      stat_push_keys_ += total;
-      stat_push_local_ += total;
-      stat_pulls_ += 1;
-      stat_pushes_ += 1;
-    }
-    return {loss, missed_t};
+    if (dev_.is_cuda()) check_step_lanes("w2v_step_fused", "D", D);
+    return step_fused_general(
+        "w2v_step_fused", {{&keys_ctr, 1}, {&keys_ctx, 1}, {&keys_neg, N}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          if (dev_.is_cuda()) {
+            w2v_sgns_step_fused_gpu(slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], loss, Bh,
+                                    (int)N, (int)D, Slab::padded(uniform_len_), 0, (float)lr,
+                                    (float)eps, current_stream(dev_));
+          } else {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            w2v_sgns_step_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], loss, Bh,
+                                         (int)N, (int)D, (float)lr, (float)eps);
+          }
+        });
   }
 
   std::tuple<torch::Tensor, torch::Tensor> mf_step_fused_general(torch::Tensor keys_w,
@@ -3158,131 +3161,88 @@ class Server {
                                                                  torch::Tensor x, int64_t R,
                                                                  double lr, double lambda,
                                                                  double eps) {
-    check_not_failed();
     TORCH_CHECK(uniform_len_ == 2 * R, "mf_step_fused: store rows must be [emb|accum] = 2R");
     TORCH_CHECK(x.scalar_type() == torch::kFloat32, "ratings must be float32");
-    for (auto* t : {&keys_w, &keys_h}) {
-      check_keys(*t);
-      check_key_range(*t);
-    }
-    int64_t B = keys_w.numel();
-    TORCH_CHECK(keys_h.numel() == B && x.numel() == B);
-    torch::Tensor loss, missed_t;
-    {
-      InflightGuard g(this);
-      auto res = resolve_fused(
-          {{keys_w.data_ptr<int64_t>(), 1}, {keys_h.data_ptr<int64_t>(), 1}}, B);
-      int64_t Bh = res.b_hit;
-      loss = torch::empty({Bh}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-      if (Bh > 0) {
-        // compact the ratings to the hit samples
-        auto xc = x.contiguous();
-        torch::Tensor xh = torch::empty({Bh}, torch::TensorOptions().dtype(torch::kFloat32));
-        {
-          const float* xp = xc.data_ptr<float>();
-          float* xo = xh.data_ptr<float>();
-          size_t mi = 0;
-          int64_t w = 0;
-          for (int64_t b = 0; b < B; ++b) {
-            if (mi < res.missed.size() && res.missed[mi] == b) { mi++; continue; }
-            xo[w++] = xp[b];
+    const int64_t B = keys_w.numel();
+    TORCH_CHECK(x.numel() == B);
+    return step_fused_general(
+        "mf_step_fused", {{&keys_w, 1}, {&keys_h, 1}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          // compact the ratings to the hit samples
+          auto xc = x.contiguous();
+          torch::Tensor xh = torch::empty({Bh}, torch::TensorOptions().dtype(torch::kFloat32));
+          {
+            const float* xp = xc.data_ptr<float>();
+            float* xo = xh.data_ptr<float>();
+            size_t mi = 0;
+            int64_t w = 0;
+            for (int64_t b = 0; b < B; ++b) {
+              if (mi < res.missed.size() && res.missed[mi] == b) { mi++; continue; }
+              xo[w++] = xp[b];
+            }
           }
-        }
-        if (dev_.is_cuda()) {
-          auto ow = offs_to_dev(res.offs[0]);
-          auto oh = offs_to_dev(res.offs[1]);
-          auto xd = xh.to(dev_, true);
-          mf_update_step_fused_gpu(slab_.data, ow.data_ptr<int64_t>(), oh.data_ptr<int64_t>(),
-                                   xd.data_ptr<float>(), loss.data_ptr<float>(), (int)Bh,
-                                   (int)R, Slab::padded(uniform_len_), 0, (float)lr,
-                                   (float)lambda, (float)eps, current_stream(dev_));
-        } else {
-          std::lock_guard<std::mutex> vg(cpu_val_mu_);
-          mf_update_step_fused_offs_cpu(slab_.data, res.offs[0].data(), res.offs[1].data(),
-                                        xh.data_ptr<float>(), loss.data_ptr<float>(), (int)Bh,
-                                        (int)R, (float)lr, (float)lambda, (float)eps);
-        }
-      }
-      missed_t = i64vec_to_tensor(res.missed);
-      int64_t total = 2 * Bh;
-      stat_pull_keys_ += total;
-      stat_pull_local_ += total;
-      stat_push_keys_ += total;
-      stat_push_local_ += total;
-      stat_pulls_ += 1;
-      stat_pushes_ += 1;
-    }
-    return {loss, missed_t};
+          if (dev_.is_cuda()) {
+            auto xd = xh.to(dev_, true);
+            mf_update_step_fused_gpu(slab_.data, res.ptr[0], res.ptr[1], xd.data_ptr<float>(),
+                                     loss, Bh, (int)R, Slab::padded(uniform_len_), 0, (float)lr,
+                                     (float)lambda, (float)eps, current_stream(dev_));
+          } else {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            mf_update_step_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[1],
+                                          xh.data_ptr<float>(), loss, Bh, (int)R, (float)lr,
+                                          (float)lambda, (float)eps);
+          }
+        });
   }
 
   torch::Tensor w2v_step_fused(torch::Tensor keys_ctr, torch::Tensor keys_ctx,
                                torch::Tensor keys_neg, int64_t N, int64_t D, double lr,
                                double eps) {
-    TORCH_CHECK(world_ == 1, "w2v_step_fused requires a single rank (all keys local)");
-    TORCH_CHECK(uniform_len_ == 2 * D, "w2v_step_fused: store rows must be [emb|accum] = 2D");
-    TORCH_CHECK(layout_identity_.load(), "w2v_step_fused requires the identity layout");
-    TORCH_CHECK(dev_.is_cuda(), "w2v_step_fused is the GPU fast path");
-    for (auto* t : {&keys_ctr, &keys_ctx, &keys_neg}) check_keys(*t);
+    check_fused_identity("w2v_step_fused", D);
+    check_step_lanes("w2v_step_fused", "D", D);
     int64_t B = keys_ctr.numel();
     TORCH_CHECK(keys_ctx.numel() == B && keys_neg.numel() == B * N);
-    auto rng_check = [&](const torch::Tensor& t) { check_key_range(t); };
-    rng_check(keys_ctr);
-    rng_check(keys_ctx);
-    rng_check(keys_neg);
+    // not stage_keys: at the SGNS bench's 459k keys per step the staged
+    // upload measured 7-23% slower than these three pageable copies
+    // (profiles/fused_skeleton_stats.txt)
+    for (auto* t : {&keys_ctr, &keys_ctx, &keys_neg}) {
+      check_keys(*t);
+      check_key_range(*t);
+    }
+    torch::Tensor dk[3] = {keys_ctr.to(dev_, true), keys_ctx.to(dev_, true),
+                           keys_neg.to(dev_, true)};
     auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    auto kc = keys_ctr.to(dev_, true);
-    auto kx = keys_ctx.to(dev_, true);
-    auto kn = keys_neg.to(dev_, true);
     {
       InflightGuard g(this);
-      w2v_sgns_step_fused_gpu(slab_.data, kc.data_ptr<int64_t>(), kx.data_ptr<int64_t>(),
-                              kn.data_ptr<int64_t>(), loss.data_ptr<float>(), (int)B, (int)N,
+      w2v_sgns_step_fused_gpu(slab_.data, dk[0].data_ptr<int64_t>(), dk[1].data_ptr<int64_t>(),
+                              dk[2].data_ptr<int64_t>(), loss.data_ptr<float>(), (int)B, (int)N,
                               (int)D, Slab::padded(uniform_len_), world_, (float)lr, (float)eps,
                               current_stream(dev_));
     }
-    int64_t total = 2 * B + B * N;
-    stat_pull_keys_ += total;
-    stat_pull_local_ += total;
-    stat_push_keys_ += total;
-    stat_push_local_ += total;
-    stat_pulls_ += 1;
-    stat_pushes_ += 1;
+    count_fused_ops(2 * B + B * N);
     return loss;
   }
 
   torch::Tensor mf_step_fused(torch::Tensor keys_w, torch::Tensor keys_h, torch::Tensor x,
                               int64_t R, double lr, double lambda, double eps) {
-    TORCH_CHECK(world_ == 1, "mf_step_fused requires a single rank (all keys local)");
-    TORCH_CHECK(uniform_len_ == 2 * R, "mf_step_fused: store rows must be [emb|accum] = 2R");
-    TORCH_CHECK(layout_identity_.load(), "mf_step_fused requires the identity layout");
-    TORCH_CHECK(dev_.is_cuda(), "mf_step_fused is the GPU fast path");
-    for (auto* t : {&keys_w, &keys_h}) check_keys(*t);
+    check_fused_identity("mf_step_fused", R);
     int64_t B = keys_w.numel();
     TORCH_CHECK(keys_h.numel() == B && x.numel() == B);
     TORCH_CHECK(x.scalar_type() == torch::kFloat32, "ratings must be float32");
-    auto rng_check = [&](const torch::Tensor& t) { check_key_range(t); };
-    rng_check(keys_w);
-    rng_check(keys_h);
+    auto sk = stage_keys("mf_step_fused", {&keys_w, &keys_h});
     auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
-    auto kw = keys_w.to(dev_, true);
-    auto kh = keys_h.to(dev_, true);
     auto xd = x.contiguous().to(dev_, true);
     {
       InflightGuard g(this);
-      mf_update_step_fused_gpu(slab_.data, kw.data_ptr<int64_t>(), kh.data_ptr<int64_t>(),
-                               xd.data_ptr<float>(), loss.data_ptr<float>(), (int)B, (int)R,
-                               Slab::padded(uniform_len_), world_, (float)lr, (float)lambda,
-                               (float)eps, current_stream(dev_));
+      mf_update_step_fused_gpu(slab_.data, sk.ptr[0], sk.ptr[1], xd.data_ptr<float>(),
+                               loss.data_ptr<float>(), (int)B, (int)R, Slab::padded(uniform_len_),
+                               world_, (float)lr, (float)lambda, (float)eps, current_stream(dev_));
     }
-    int64_t total = 2 * B;
-    stat_pull_keys_ += total;
-    stat_pull_local_ += total;
-    stat_push_keys_ += total;
-    stat_push_local_ += total;
-    stat_pulls_ += 1;
-    stat_pushes_ += 1;
+    count_fused_ops(2 * B);
     return loss;
   }
+
 
   // --------------------------------------------- spill-tier rebalance
 
@@ -3786,6 +3746,7 @@ void kge_complex_step(torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::
   int B = (int)loss.numel();
   if (s.is_cuda()) {
     TORCH_CHECK(hip_available(), "kge_complex_step: CUDA tensor but no HIP device");
+    check_step_lanes("kge_complex_step", "D/2", D / 2);
     kge_complex_step_gpu(cfp(s), cfp(r), cfp(o), cfp(neg), fp(ds), fp(dr), fp(do_), fp(dneg),
                          fp(loss), B, (int)N, (int)D, (float)lr, (float)eps,
                          current_stream(s.device()));
@@ -3906,6 +3867,7 @@ void w2v_sgns_step(torch::Tensor ctr, torch::Tensor ctx, torch::Tensor neg, torc
   int B = (int)loss.numel();
   if (ctr.is_cuda()) {
     TORCH_CHECK(hip_available(), "w2v_sgns_step: CUDA tensor but no HIP device");
+    check_step_lanes("w2v_sgns_step", "D", D);
     w2v_sgns_step_gpu(cfp(ctr), cfp(ctx), cfp(neg), fp(dctr), fp(dctx), fp(dneg), fp(loss), B,
                       (int)N, (int)D, (float)lr, (float)eps, current_stream(ctr.device()));
   } else {

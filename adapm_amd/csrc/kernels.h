@@ -14,6 +14,12 @@
 
 namespace adapm {
 
+// The ComplEx and SGNS step kernels (classic and fused) hold a row's lanes
+// in registers, at most 8 per thread of a 256-thread workgroup. ComplEx has
+// D/2 lanes per row, SGNS D. Callers refuse longer rows before launching;
+// the CPU twins have no such limit.
+constexpr int STEP_MAX_LANES = 8 * 256;
+
 // ComplEx training step over B positives with N o-side negatives each.
 //  s, r, o:   [B][2D]   pulled rows (emb | accum)
 //  neg:       [B*N][2D] pulled negative-entity rows
@@ -65,9 +71,8 @@ void rowmark_clear_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream);
 // all-local samples, remote ones take the classic path).
 void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
                                 const int64_t* keys_o, const int64_t* keys_neg, float* loss,
-                                int B, int N, int D, int32_t plen, int world, int rank,
-                                float lr, float eps, void* stream,
-                                const uint32_t* marks = nullptr,
+                                int B, int N, int D, int32_t plen, int world, float lr,
+                                float eps, void* stream, const uint32_t* marks = nullptr,
                                 unsigned long long* shared_stat = nullptr);
 
 // CPU tier of the offsets-mode fused steps (exercises the world>1 fused
@@ -82,10 +87,11 @@ void mf_update_step_fused_offs_cpu(float* slab, const int64_t* offs_w, const int
                                    const float* x, float* loss, int B, int R, float lr,
                                    float lambda, float eps);
 
-// FUSED SGNS step (slab-direct reads + AdaGrad writes like
-// kge_complex_step_fused_gpu, but every write is still atomic: the ComplEx
-// step is plain on rows unique in the batch, atomic on shared ones, and
-// this step can adopt the same row marks).
+// FUSED SGNS step: slab-direct reads + AdaGrad writes, same addressing
+// modes as kge_complex_step_fused_gpu. Every write is atomic: the kernel
+// takes no row marks. It writes through the same per-lane helper as the
+// ComplEx step (slab_adagrad in kernels_hip.hip) with shared = true, so
+// adopting the marks means passing a row's mark there instead.
 void w2v_sgns_step_fused_gpu(float* slab, const int64_t* keys_ctr, const int64_t* keys_ctx,
                              const int64_t* keys_neg, float* loss, int B, int N, int D,
                              int32_t plen, int world, float lr, float eps, void* stream);

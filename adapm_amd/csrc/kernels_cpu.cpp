@@ -141,6 +141,14 @@ void mf_update_step_cpu(const float* w, const float* h, const float* x, float* d
   }
 }
 
+// In-place AdaGrad of one slab element: emb += delta(g), acc += g^2, with
+// the delta taken from the accumulator as it was.
+static inline void adagrad_inplace(float& emb, float& acc, float g, float lr, float eps) {
+  float G = acc + g * g;
+  emb += -lr * g / std::sqrt(G + eps);
+  acc += g * g;
+}
+
 // Fused slab-direct steps, offsets mode (CPU tier of the world>1 fused
 // path: offs_* carry float offsets into the slab, resolved by the host
 // metadata pass; math mirrors the GPU fused kernels — object rows are
@@ -172,28 +180,15 @@ void kge_complex_step_fused_offs_cpu(float* slab, const int64_t* offs_s, const i
         a_sim[k] += c * (rb[k] * o_im - rb[dc + k] * o_re);
         a_rre[k] += c * (sb[k] * o_re + sb[dc + k] * o_im);
         a_rim[k] += c * (sb[k] * o_im - sb[dc + k] * o_re);
-        float g_re = c * u_re[k], g_im = c * u_im[k];
-        float G_re = ob[D + k] + g_re * g_re;
-        float G_im = ob[D + dc + k] + g_im * g_im;
-        ob[k] += -lr * g_re / std::sqrt(G_re + eps);
-        ob[dc + k] += -lr * g_im / std::sqrt(G_im + eps);
-        ob[D + k] += g_re * g_re;
-        ob[D + dc + k] += g_im * g_im;
+        adagrad_inplace(ob[k], ob[D + k], c * u_re[k], lr, eps);
+        adagrad_inplace(ob[dc + k], ob[D + dc + k], c * u_im[k], lr, eps);
       }
     }
     for (int k = 0; k < dc; ++k) {
-      float Gsr = sb[D + k] + a_sre[k] * a_sre[k];
-      float Gsi = sb[D + dc + k] + a_sim[k] * a_sim[k];
-      sb[k] += -lr * a_sre[k] / std::sqrt(Gsr + eps);
-      sb[dc + k] += -lr * a_sim[k] / std::sqrt(Gsi + eps);
-      sb[D + k] += a_sre[k] * a_sre[k];
-      sb[D + dc + k] += a_sim[k] * a_sim[k];
-      float Grr = rb[D + k] + a_rre[k] * a_rre[k];
-      float Gri = rb[D + dc + k] + a_rim[k] * a_rim[k];
-      rb[k] += -lr * a_rre[k] / std::sqrt(Grr + eps);
-      rb[dc + k] += -lr * a_rim[k] / std::sqrt(Gri + eps);
-      rb[D + k] += a_rre[k] * a_rre[k];
-      rb[D + dc + k] += a_rim[k] * a_rim[k];
+      adagrad_inplace(sb[k], sb[D + k], a_sre[k], lr, eps);
+      adagrad_inplace(sb[dc + k], sb[D + dc + k], a_sim[k], lr, eps);
+      adagrad_inplace(rb[k], rb[D + k], a_rre[k], lr, eps);
+      adagrad_inplace(rb[dc + k], rb[D + dc + k], a_rim[k], lr, eps);
     }
     loss[b] = lsum;
   }
@@ -220,16 +215,11 @@ void w2v_sgns_step_fused_offs_cpu(float* slab, const int64_t* offs_ctr, const in
       for (int k = 0; k < D; ++k) {
         float xv = xb[k];
         a_c[k] += g * xv;
-        float gx = g * c_emb[k];
-        float G = xb[D + k] + gx * gx;
-        xb[k] += -lr * gx / std::sqrt(G + eps);
-        xb[D + k] += gx * gx;
+        adagrad_inplace(xb[k], xb[D + k], g * c_emb[k], lr, eps);
       }
     }
     for (int k = 0; k < D; ++k) {
-      float G = cb[D + k] + a_c[k] * a_c[k];
-      cb[k] += -lr * a_c[k] / std::sqrt(G + eps);
-      cb[D + k] += a_c[k] * a_c[k];
+      adagrad_inplace(cb[k], cb[D + k], a_c[k], lr, eps);
     }
     loss[b] = lsum;
   }
@@ -249,12 +239,8 @@ void mf_update_step_fused_offs_cpu(float* slab, const int64_t* offs_w, const int
       float wv = wb[k], hv = hb[k];
       float gw = -2.f * e * hv + 2.f * lambda * wv;
       float gh = -2.f * e * wv + 2.f * lambda * hv;
-      float Gw = wb[R + k] + gw * gw;
-      float Gh = hb[R + k] + gh * gh;
-      wb[k] += -lr * gw / std::sqrt(Gw + eps);
-      wb[R + k] += gw * gw;
-      hb[k] += -lr * gh / std::sqrt(Gh + eps);
-      hb[R + k] += gh * gh;
+      adagrad_inplace(wb[k], wb[R + k], gw, lr, eps);
+      adagrad_inplace(hb[k], hb[R + k], gh, lr, eps);
     }
   }
 }

@@ -7,6 +7,7 @@
 // LDS hop across the 4 waves).
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <type_traits>
 
 #include "kernels.h"
 #include "ustream.h"
@@ -14,6 +15,25 @@
 namespace adapm {
 
 #define KT 256  // threads per workgroup
+
+// Blocks for n grid-strided work items: at least one (an empty batch is a
+// launch whose loop never runs), at most `cap`.
+static inline unsigned grid_for(int64_t n, int64_t cap = 16384) {
+  return (unsigned)std::min(std::max<int64_t>(n, 1), cap);
+}
+
+// The step kernels keep a row's lanes in registers, KPT per thread, so KPT
+// is a template argument: f receives it as std::integral_constant<int, KPT>
+// for the smallest KPT of 1, 2, 4, 8 that covers `lanes`. The entry points
+// refuse rows of more than STEP_MAX_LANES lanes before they get here.
+static_assert(STEP_MAX_LANES == 8 * KT, "dispatch_kpt stops at KPT = 8");
+template <typename F>
+static inline void dispatch_kpt(int lanes, F&& f) {
+  if (lanes <= KT) f(std::integral_constant<int, 1>{});
+  else if (lanes <= 2 * KT) f(std::integral_constant<int, 2>{});
+  else if (lanes <= 4 * KT) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
+}
 
 __device__ inline float block_reduce_sum(float v, float* lds) {
   // wave-level reduce (64 lanes)
@@ -37,6 +57,20 @@ __device__ inline float sigmoidf(float x) { return 1.f / (1.f + __expf(-x)); }
 __device__ inline float softplusf(float x) {
   // log(1+exp(x)), stable
   return x > 20.f ? x : __logf(1.f + __expf(x));
+}
+
+// AdaGrad: the embedding delta for gradient g, given the accumulator value
+// `acc` the lane read (G in the row's second half).
+__device__ inline float adagrad_delta(float g, float acc, float lr, float eps) {
+  float G = acc + g * g;
+  return -lr * g * __frsqrt_rn(G + eps);
+}
+
+// Classic kernels: the push-ready pair [delta | g^2] of one lane.
+__device__ inline void write_delta(float* d_emb, float* d_acc, float g, float acc, float lr,
+                                   float eps) {
+  *d_emb = adagrad_delta(g, acc, lr, eps);
+  *d_acc = g * g;
 }
 
 // --------------------------------------------------------------- ComplEx
@@ -108,14 +142,8 @@ __global__ void k_kge_step(const float* __restrict__ s, const float* __restrict_
         a_rre[i] += c * (s_re[i] * o_re[i] + s_im[i] * o_im[i]);
         a_rim[i] += c * (s_re[i] * o_im[i] - s_im[i] * o_re[i]);
         // o grad + fused AdaGrad (G in the row's second half)
-        float g_re = c * u_re[i];
-        float g_im = c * u_im[i];
-        float G_re = ob[D + k] + g_re * g_re;
-        float G_im = ob[D + dc + k] + g_im * g_im;
-        dob[k] = -lr * g_re * __frsqrt_rn(G_re + eps);
-        dob[dc + k] = -lr * g_im * __frsqrt_rn(G_im + eps);
-        dob[D + k] = g_re * g_re;
-        dob[D + dc + k] = g_im * g_im;
+        write_delta(&dob[k], &dob[D + k], c * u_re[i], ob[D + k], lr, eps);
+        write_delta(&dob[dc + k], &dob[D + dc + k], c * u_im[i], ob[D + dc + k], lr, eps);
       }
     }
     // write s/r deltas with fused AdaGrad
@@ -125,18 +153,10 @@ __global__ void k_kge_step(const float* __restrict__ s, const float* __restrict_
     for (int i = 0; i < KPT; ++i) {
       int k = threadIdx.x + i * KT;
       if (k >= dc) continue;
-      float Gsr = sb[D + k] + a_sre[i] * a_sre[i];
-      float Gsi = sb[D + dc + k] + a_sim[i] * a_sim[i];
-      dsb[k] = -lr * a_sre[i] * __frsqrt_rn(Gsr + eps);
-      dsb[dc + k] = -lr * a_sim[i] * __frsqrt_rn(Gsi + eps);
-      dsb[D + k] = a_sre[i] * a_sre[i];
-      dsb[D + dc + k] = a_sim[i] * a_sim[i];
-      float Grr = rb[D + k] + a_rre[i] * a_rre[i];
-      float Gri = rb[D + dc + k] + a_rim[i] * a_rim[i];
-      drb[k] = -lr * a_rre[i] * __frsqrt_rn(Grr + eps);
-      drb[dc + k] = -lr * a_rim[i] * __frsqrt_rn(Gri + eps);
-      drb[D + k] = a_rre[i] * a_rre[i];
-      drb[D + dc + k] = a_rim[i] * a_rim[i];
+      write_delta(&dsb[k], &dsb[D + k], a_sre[i], sb[D + k], lr, eps);
+      write_delta(&dsb[dc + k], &dsb[D + dc + k], a_sim[i], sb[D + dc + k], lr, eps);
+      write_delta(&drb[k], &drb[D + k], a_rre[i], rb[D + k], lr, eps);
+      write_delta(&drb[dc + k], &drb[D + dc + k], a_rim[i], rb[D + dc + k], lr, eps);
     }
     if (threadIdx.x == 0) loss[b] = lsum;
   }
@@ -206,10 +226,7 @@ __global__ void k_w2v_step(const float* __restrict__ ctr, const float* __restric
         int k = threadIdx.x + i * KT;
         if (k >= D) continue;
         a_c[i] += g * x_emb[i];
-        float gx = g * c_emb[i];
-        float G = xb[D + k] + gx * gx;
-        dxb[k] = -lr * gx * __frsqrt_rn(G + eps);
-        dxb[D + k] = gx * gx;
+        write_delta(&dxb[k], &dxb[D + k], g * c_emb[i], xb[D + k], lr, eps);
       }
     }
     float* dcb = dctr + (int64_t)b * row;
@@ -217,9 +234,7 @@ __global__ void k_w2v_step(const float* __restrict__ ctr, const float* __restric
     for (int i = 0; i < KPT; ++i) {
       int k = threadIdx.x + i * KT;
       if (k >= D) continue;
-      float G = cb[D + k] + a_c[i] * a_c[i];
-      dcb[k] = -lr * a_c[i] * __frsqrt_rn(G + eps);
-      dcb[D + k] = a_c[i] * a_c[i];
+      write_delta(&dcb[k], &dcb[D + k], a_c[i], cb[D + k], lr, eps);
     }
     if (threadIdx.x == 0) loss[b] = lsum;
   }
@@ -246,12 +261,8 @@ __global__ void k_mf_step(const float* __restrict__ w, const float* __restrict__
     for (int k = threadIdx.x; k < R; k += KT) {
       float gw = -2.f * e * hb[k] + 2.f * lambda * wb[k];
       float gh = -2.f * e * wb[k] + 2.f * lambda * hb[k];
-      float Gw = wb[R + k] + gw * gw;
-      float Gh = hb[R + k] + gh * gh;
-      dwb[k] = -lr * gw * __frsqrt_rn(Gw + eps);
-      dwb[R + k] = gw * gw;
-      dhb[k] = -lr * gh * __frsqrt_rn(Gh + eps);
-      dhb[R + k] = gh * gh;
+      write_delta(&dwb[k], &dwb[R + k], gw, wb[R + k], lr, eps);
+      write_delta(&dhb[k], &dhb[R + k], gh, hb[R + k], lr, eps);
     }
   }
 }
@@ -290,8 +301,7 @@ __global__ void k_mf_loss(const float* __restrict__ w, const float* __restrict__
 void mf_loss_gpu(const float* w, const float* h, const float* x, float* out2, int B, int R,
                  float lambda, void* stream) {
   if (B < 1) return;
-  int g = B > 16384 ? 16384 : B;
-  hipLaunchKernelGGL(k_mf_loss, dim3(g), dim3(KT), 0, (hipStream_t)stream, w, h, x,
+  hipLaunchKernelGGL(k_mf_loss, dim3(grid_for(B)), dim3(KT), 0, (hipStream_t)stream, w, h, x,
                      out2, B, R, lambda);
 }
 
@@ -318,25 +328,14 @@ __global__ void k_alias_draw(const float* __restrict__ prob, const int32_t* __re
 
 // --------------------------------------------------------------- launchers
 
-static inline int grid_for(int64_t n) {
-  int64_t g = n < 1 ? 1 : n;
-  return (int)(g > 16384 ? 16384 : g);
-}
-
 void kge_complex_step_gpu(const float* s, const float* r, const float* o, const float* neg,
                           float* ds, float* dr, float* do_, float* dneg, float* loss, int B,
                           int N, int D, float lr, float eps, void* stream) {
-  int dc = D >> 1;
-  dim3 g(grid_for(B)), t(KT);
-  auto st = (hipStream_t)stream;
-#define LAUNCH(KPT) \
-  hipLaunchKernelGGL(k_kge_step<KPT>, g, t, 0, st, s, r, o, neg, ds, dr, do_, dneg, loss, B, N, \
-                     D, lr, eps)
-  if (dc <= KT) LAUNCH(1);
-  else if (dc <= 2 * KT) LAUNCH(2);
-  else if (dc <= 4 * KT) LAUNCH(4);
-  else LAUNCH(8);
-#undef LAUNCH
+  dispatch_kpt(D >> 1, [&](auto kpt) {
+    hipLaunchKernelGGL(k_kge_step<decltype(kpt)::value>, dim3(grid_for(B)), dim3(KT), 0,
+                       (hipStream_t)stream, s, r, o, neg, ds, dr, do_, dneg, loss, B, N, D, lr,
+                       eps);
+  });
 }
 void kge_complex_score_gpu(const float* s, const float* r, const float* cand, float* scores,
                            int B, int E, int D, void* stream) {
@@ -346,16 +345,11 @@ void kge_complex_score_gpu(const float* s, const float* r, const float* cand, fl
 void w2v_sgns_step_gpu(const float* ctr, const float* ctx, const float* neg, float* dctr,
                        float* dctx, float* dneg, float* loss, int B, int N, int D, float lr,
                        float eps, void* stream) {
-  dim3 g(grid_for(B)), t(KT);
-  auto st = (hipStream_t)stream;
-#define LAUNCH(KPT) \
-  hipLaunchKernelGGL(k_w2v_step<KPT>, g, t, 0, st, ctr, ctx, neg, dctr, dctx, dneg, loss, B, N, \
-                     D, lr, eps)
-  if (D <= KT) LAUNCH(1);
-  else if (D <= 2 * KT) LAUNCH(2);
-  else if (D <= 4 * KT) LAUNCH(4);
-  else LAUNCH(8);
-#undef LAUNCH
+  dispatch_kpt(D, [&](auto kpt) {
+    hipLaunchKernelGGL(k_w2v_step<decltype(kpt)::value>, dim3(grid_for(B)), dim3(KT), 0,
+                       (hipStream_t)stream, ctr, ctx, neg, dctr, dctx, dneg, loss, B, N, D, lr,
+                       eps);
+  });
 }
 void mf_update_step_gpu(const float* w, const float* h, const float* x, float* dw, float* dh,
                         float* loss, int B, int R, float lr, float lambda, float eps,
@@ -370,9 +364,8 @@ namespace adapm {
 void alias_draw_gpu(const float* prob, const int32_t* alias, int64_t n, uint64_t seed,
                     int64_t N, int64_t* out, void* stream) {
   if (N == 0) return;
-  int blocks = (int)std::min<int64_t>((N + 255) / 256, 4096);
-  hipLaunchKernelGGL(k_alias_draw, dim3(blocks), dim3(256), 0, (hipStream_t)stream, prob, alias,
-                     n, seed, N, out);
+  hipLaunchKernelGGL(k_alias_draw, dim3(grid_for((N + 255) / 256, 4096)), dim3(256), 0,
+                     (hipStream_t)stream, prob, alias, n, seed, N, out);
 }
 }  // namespace adapm
 
@@ -553,9 +546,7 @@ __global__ void k_rescal_step(const float* __restrict__ s, const float* __restri
       if (threadIdx.x == 0) lsum += softplusf(-y * dot);
       for (int k = threadIdx.x; k < D; k += KT) {
         w[k] += c * ob[k];  // single writer per k: thread-private index
-        float g = c * u[k];
-        dob[k] = -lr * g * __frsqrt_rn(ob[D + k] + g * g + eps);
-        dob[D + k] = g * g;
+        write_delta(&dob[k], &dob[D + k], c * u[k], ob[D + k], lr, eps);
       }
       __syncthreads();
     }
@@ -566,17 +557,14 @@ __global__ void k_rescal_step(const float* __restrict__ s, const float* __restri
     for (int i = threadIdx.x; i < D; i += KT) {
       float a = 0.f;
       for (int k = 0; k < D; ++k) a += Rm[i * D + k] * w[k];
-      float g = a;
-      dsb[i] = -lr * g * __frsqrt_rn(sb[D + i] + g * g + eps);
-      dsb[D + i] = g * g;
+      write_delta(&dsb[i], &dsb[D + i], a, sb[D + i], lr, eps);
     }
     // dR = e_s w^T
     float* drb = drl + (int64_t)b * rrow;
     for (int idx = threadIdx.x; idx < D * D; idx += KT) {
       int i = idx / D, k = idx % D;
-      float g = es[i] * w[k];
-      drb[idx] = -lr * g * __frsqrt_rn(rb[(int64_t)D * D + idx] + g * g + eps);
-      drb[(int64_t)D * D + idx] = g * g;
+      const int64_t acc = (int64_t)D * D + idx;
+      write_delta(&drb[idx], &drb[acc], es[i] * w[k], rb[acc], lr, eps);
     }
     __syncthreads();
   }
@@ -586,9 +574,9 @@ void rescal_step_gpu(const float* s, const float* r, const float* o, const float
                      float* ds, float* drl, float* do_, float* dneg, float* loss, int B, int N,
                      int D, float lr, float eps, void* stream) {
   size_t smem = (size_t)(D * D + 3 * D + KT / 64) * sizeof(float);
-  int blocks = (int)std::min<int64_t>(B, 8192);
-  hipLaunchKernelGGL(k_rescal_step, dim3(blocks), dim3(KT), smem, (hipStream_t)stream, s, r, o,
-                     neg, ds, drl, do_, dneg, loss, B, N, D, lr, eps);
+  if (B < 1) return;
+  hipLaunchKernelGGL(k_rescal_step, dim3(grid_for(B, 8192)), dim3(KT), smem, (hipStream_t)stream,
+                     s, r, o, neg, ds, drl, do_, dneg, loss, B, N, D, lr, eps);
 }
 
 }  // namespace adapm
@@ -671,6 +659,50 @@ __device__ inline float plain_add(float a, float delta) {
   return a + delta;
 }
 
+// Fused kernels: one lane's AdaGrad update applied to the slab row itself,
+// *p_emb += delta and *p_acc += g^2. A row shared with another occurrence
+// of the batch takes atomics; the only writer of a row stores over the
+// values (emb, acc) it read. The SGNS and MF steps have no row marks and
+// pass shared = true.
+__device__ inline void slab_adagrad(float* p_emb, float* p_acc, float g, float emb, float acc,
+                                    float lr, float eps, bool shared) {
+  float d = adagrad_delta(g, acc, lr, eps);
+  if (shared) {
+    atomicAdd(p_emb, d);
+    atomicAdd(p_acc, g * g);
+  } else {
+    *p_emb = plain_add(emb, d);
+    *p_acc = plain_add(acc, g * g);
+  }
+}
+
+// slab_adagrad for a complex lane (re at k, im at dc + k) of the fused ComplEx
+// step, both halves under one branch. A macro on purpose, and the only one:
+// the KPT = 8 instantiations of k_kge_step_fused spill, and their register
+// allocation is so sensitive that moving these statements into an inlined
+// function (even just calling adagrad_delta here) adds 44-120 bytes of
+// scratch per lane and 15-17% to the D = 4096 step
+// (profiles/fused_skeleton_stats.txt). Expands in a scope with k, dc, D, lr,
+// eps.
+#define SLAB_ADAGRAD_COMPLEX(row, shared, g_re, g_im, emb_re, emb_im, acc_re, acc_im) \
+  do {                                                                                \
+    float G_re = (acc_re) + (g_re) * (g_re);                                          \
+    float G_im = (acc_im) + (g_im) * (g_im);                                          \
+    float d_re = -lr * (g_re) * __frsqrt_rn(G_re + eps);                              \
+    float d_im = -lr * (g_im) * __frsqrt_rn(G_im + eps);                              \
+    if (shared) {                                                                     \
+      atomicAdd(&(row)[k], d_re);                                                     \
+      atomicAdd(&(row)[dc + k], d_im);                                                \
+      atomicAdd(&(row)[D + k], (g_re) * (g_re));                                      \
+      atomicAdd(&(row)[D + dc + k], (g_im) * (g_im));                                 \
+    } else {                                                                          \
+      (row)[k] = plain_add(emb_re, d_re);                                             \
+      (row)[dc + k] = plain_add(emb_im, d_im);                                        \
+      (row)[D + k] = plain_add(acc_re, (g_re) * (g_re));                              \
+      (row)[D + dc + k] = plain_add(acc_im, (g_im) * (g_im));                         \
+    }                                                                                 \
+  } while (0)
+
 // Fused ComplEx step — see kernels.h. Structure mirrors k_kge_step but
 // rows come from / return to the slab itself. UNIQ = false is the
 // all-atomic kernel (marks unused); UNIQ = true writes the rows that
@@ -680,8 +712,8 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
                                  const int64_t* __restrict__ keys_r,
                                  const int64_t* __restrict__ keys_o,
                                  const int64_t* __restrict__ keys_neg, float* __restrict__ loss,
-                                 int B, int N, int D, int32_t plen, int world, int rank,
-                                 float lr, float eps, const uint32_t* __restrict__ marks,
+                                 int B, int N, int D, int32_t plen, int world, float lr,
+                                 float eps, const uint32_t* __restrict__ marks,
                                  unsigned long long* __restrict__ shared_stat) {
   __shared__ float lds[KT / 64];
   const int dc = D >> 1;
@@ -749,22 +781,7 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
         a_rim[i] += c * (s_re[i] * o_im[i] - s_im[i] * o_re[i]);
         float g_re = c * u_re[i];
         float g_im = c * u_im[i];
-        float G_re = Go_re[i] + g_re * g_re;
-        float G_im = Go_im[i] + g_im * g_im;
-        float d_re = -lr * g_re * __frsqrt_rn(G_re + eps);
-        float d_im = -lr * g_im * __frsqrt_rn(G_im + eps);
-        if (o_shared) {
-          atomicAdd(&ob[k], d_re);
-          atomicAdd(&ob[dc + k], d_im);
-          atomicAdd(&ob[D + k], g_re * g_re);
-          atomicAdd(&ob[D + dc + k], g_im * g_im);
-        } else {
-          // only writer of this row in this launch: same sums, plain stores
-          ob[k] = plain_add(o_re[i], d_re);
-          ob[dc + k] = plain_add(o_im[i], d_im);
-          ob[D + k] = plain_add(Go_re[i], g_re * g_re);
-          ob[D + dc + k] = plain_add(Go_im[i], g_im * g_im);
-        }
+        SLAB_ADAGRAD_COMPLEX(ob, o_shared, g_re, g_im, o_re[i], o_im[i], Go_re[i], Go_im[i]);
       }
     }
     float* dsb = const_cast<float*>(sb);
@@ -774,37 +791,9 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
       int k = threadIdx.x + i * KT;
       if (k >= dc) continue;
       float Gs_re = sb[D + k], Gs_im = sb[D + dc + k];
-      float Gsr = Gs_re + a_sre[i] * a_sre[i];
-      float Gsi = Gs_im + a_sim[i] * a_sim[i];
-      float ds_re = -lr * a_sre[i] * __frsqrt_rn(Gsr + eps);
-      float ds_im = -lr * a_sim[i] * __frsqrt_rn(Gsi + eps);
-      if (s_shared) {
-        atomicAdd(&dsb[k], ds_re);
-        atomicAdd(&dsb[dc + k], ds_im);
-        atomicAdd(&dsb[D + k], a_sre[i] * a_sre[i]);
-        atomicAdd(&dsb[D + dc + k], a_sim[i] * a_sim[i]);
-      } else {
-        dsb[k] = plain_add(s_re[i], ds_re);
-        dsb[dc + k] = plain_add(s_im[i], ds_im);
-        dsb[D + k] = plain_add(Gs_re, a_sre[i] * a_sre[i]);
-        dsb[D + dc + k] = plain_add(Gs_im, a_sim[i] * a_sim[i]);
-      }
+      SLAB_ADAGRAD_COMPLEX(dsb, s_shared, a_sre[i], a_sim[i], s_re[i], s_im[i], Gs_re, Gs_im);
       float Gr_re = rb[D + k], Gr_im = rb[D + dc + k];
-      float Grr = Gr_re + a_rre[i] * a_rre[i];
-      float Gri = Gr_im + a_rim[i] * a_rim[i];
-      float dr_re = -lr * a_rre[i] * __frsqrt_rn(Grr + eps);
-      float dr_im = -lr * a_rim[i] * __frsqrt_rn(Gri + eps);
-      if (r_shared) {
-        atomicAdd(&drb[k], dr_re);
-        atomicAdd(&drb[dc + k], dr_im);
-        atomicAdd(&drb[D + k], a_rre[i] * a_rre[i]);
-        atomicAdd(&drb[D + dc + k], a_rim[i] * a_rim[i]);
-      } else {
-        drb[k] = plain_add(r_re[i], dr_re);
-        drb[dc + k] = plain_add(r_im[i], dr_im);
-        drb[D + k] = plain_add(Gr_re, a_rre[i] * a_rre[i]);
-        drb[D + dc + k] = plain_add(Gr_im, a_rim[i] * a_rim[i]);
-      }
+      SLAB_ADAGRAD_COMPLEX(drb, r_shared, a_rre[i], a_rim[i], r_re[i], r_im[i], Gr_re, Gr_im);
     }
     if (threadIdx.x == 0) {
       loss[b] = lsum;
@@ -813,33 +802,25 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
   }
 }
 
+#undef SLAB_ADAGRAD_COMPLEX
+
 void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
                                 const int64_t* keys_o, const int64_t* keys_neg, float* loss,
-                                int B, int N, int D, int32_t plen, int world, int rank,
-                                float lr, float eps, void* stream, const uint32_t* marks,
+                                int B, int N, int D, int32_t plen, int world, float lr,
+                                float eps, void* stream, const uint32_t* marks,
                                 unsigned long long* shared_stat) {
-  int dc = D >> 1;
-  dim3 g((unsigned)std::min<int64_t>(B, 16384)), t(KT);
-  auto st = (hipStream_t)stream;
+  if (B < 1) return;  // unlike the other steps, an empty batch enqueues nothing
   // marks are indexed by key, which is the row only in the single-rank
   // identity layout; every other addressing mode stays all-atomic
   const bool uniq = marks != nullptr && world == 1;
-#define LAUNCHF(KPT)                                                                        \
-  do {                                                                                      \
-    if (uniq)                                                                               \
-      hipLaunchKernelGGL((k_kge_step_fused<KPT, true>), g, t, 0, st, slab, keys_s, keys_r,  \
-                         keys_o, keys_neg, loss, B, N, D, plen, world, rank, lr, eps, marks, \
-                         shared_stat);                                                      \
-    else                                                                                    \
-      hipLaunchKernelGGL((k_kge_step_fused<KPT, false>), g, t, 0, st, slab, keys_s, keys_r, \
-                         keys_o, keys_neg, loss, B, N, D, plen, world, rank, lr, eps,       \
-                         (const uint32_t*)nullptr, (unsigned long long*)nullptr);           \
-  } while (0)
-  if (dc <= KT) LAUNCHF(1);
-  else if (dc <= 2 * KT) LAUNCHF(2);
-  else if (dc <= 4 * KT) LAUNCHF(4);
-  else LAUNCHF(8);
-#undef LAUNCHF
+  if (!uniq) marks = nullptr, shared_stat = nullptr;
+  dispatch_kpt(D >> 1, [&](auto kpt) {
+    constexpr int KPT = decltype(kpt)::value;
+    hipLaunchKernelGGL((uniq ? k_kge_step_fused<KPT, true> : k_kge_step_fused<KPT, false>),
+                       dim3(grid_for(B)), dim3(KT), 0, (hipStream_t)stream, slab, keys_s, keys_r,
+                       keys_o, keys_neg, loss, B, N, D, plen, world, lr, eps, marks,
+                       shared_stat);
+  });
 }
 
 }  // namespace adapm
@@ -885,19 +866,15 @@ __global__ void k_w2v_step_fused(float* __restrict__ slab, const int64_t* __rest
         int k = threadIdx.x + i * KT;
         if (k >= D) continue;
         a_c[i] += g * x_emb[i];
-        float gx = g * c_emb[i];
-        float G = xb[D + k] + gx * gx;
-        atomicAdd(&xb[k], -lr * gx * __frsqrt_rn(G + eps));
-        atomicAdd(&xb[D + k], gx * gx);
+        slab_adagrad(&xb[k], &xb[D + k], g * c_emb[i], x_emb[i], xb[D + k], lr, eps,
+                     /*shared=*/true);
       }
     }
 #pragma unroll
     for (int i = 0; i < KPT; ++i) {
       int k = threadIdx.x + i * KT;
       if (k >= D) continue;
-      float G = cb[D + k] + a_c[i] * a_c[i];
-      atomicAdd(&cb[k], -lr * a_c[i] * __frsqrt_rn(G + eps));
-      atomicAdd(&cb[D + k], a_c[i] * a_c[i]);
+      slab_adagrad(&cb[k], &cb[D + k], a_c[i], c_emb[i], cb[D + k], lr, eps, /*shared=*/true);
     }
     if (threadIdx.x == 0) loss[b] = lsum;
   }
@@ -923,12 +900,9 @@ __global__ void k_mf_step_fused(float* __restrict__ slab, const int64_t* __restr
       float wv = wb[k], hv = hb[k];
       float gw = -2.f * e * hv + 2.f * lambda * wv;
       float gh = -2.f * e * wv + 2.f * lambda * hv;
-      float Gw = wb[R + k] + gw * gw;
-      float Gh = hb[R + k] + gh * gh;
-      atomicAdd(&wb[k], -lr * gw * __frsqrt_rn(Gw + eps));
-      atomicAdd(&wb[R + k], gw * gw);
-      atomicAdd(&hb[k], -lr * gh * __frsqrt_rn(Gh + eps));
-      atomicAdd(&hb[R + k], gh * gh);
+      float Gw = wb[R + k], Gh = hb[R + k];
+      slab_adagrad(&wb[k], &wb[R + k], gw, wv, Gw, lr, eps, /*shared=*/true);
+      slab_adagrad(&hb[k], &hb[R + k], gh, hv, Gh, lr, eps, /*shared=*/true);
     }
   }
 }
@@ -936,24 +910,18 @@ __global__ void k_mf_step_fused(float* __restrict__ slab, const int64_t* __restr
 void w2v_sgns_step_fused_gpu(float* slab, const int64_t* keys_ctr, const int64_t* keys_ctx,
                              const int64_t* keys_neg, float* loss, int B, int N, int D,
                              int32_t plen, int world, float lr, float eps, void* stream) {
-  dim3 g((unsigned)std::min<int64_t>(B < 1 ? 1 : B, 16384)), t(KT);
-  auto st = (hipStream_t)stream;
-#define LAUNCHW(KPT) \
-  hipLaunchKernelGGL(k_w2v_step_fused<KPT>, g, t, 0, st, slab, keys_ctr, keys_ctx, keys_neg, \
-                     loss, B, N, D, plen, world, lr, eps)
-  if (D <= KT) LAUNCHW(1);
-  else if (D <= 2 * KT) LAUNCHW(2);
-  else if (D <= 4 * KT) LAUNCHW(4);
-  else LAUNCHW(8);
-#undef LAUNCHW
+  dispatch_kpt(D, [&](auto kpt) {
+    hipLaunchKernelGGL(k_w2v_step_fused<decltype(kpt)::value>, dim3(grid_for(B)), dim3(KT), 0,
+                       (hipStream_t)stream, slab, keys_ctr, keys_ctx, keys_neg, loss, B, N, D,
+                       plen, world, lr, eps);
+  });
 }
 
 void mf_update_step_fused_gpu(float* slab, const int64_t* keys_w, const int64_t* keys_h,
                               const float* x, float* loss, int B, int R, int32_t plen,
                               int world, float lr, float lambda, float eps, void* stream) {
-  hipLaunchKernelGGL(k_mf_step_fused, dim3((unsigned)std::min<int64_t>(B < 1 ? 1 : B, 16384)),
-                     dim3(KT), 0, (hipStream_t)stream, slab, keys_w, keys_h, x, loss, B, R,
-                     plen, world, lr, lambda, eps);
+  hipLaunchKernelGGL(k_mf_step_fused, dim3(grid_for(B)), dim3(KT), 0, (hipStream_t)stream, slab,
+                     keys_w, keys_h, x, loss, B, R, plen, world, lr, lambda, eps);
 }
 
 }  // namespace adapm

@@ -347,12 +347,13 @@ def test_kge_fused_matches_classic():
 
 
 @pytest.mark.gpu
-def test_w2v_fused_matches_classic():
+@pytest.mark.parametrize("D", [48, 300, 520, 1100])  # 1, 2, 4, 8 lanes per thread
+def test_w2v_fused_matches_classic(D):
     import adapm_amd
 
     adapm_amd._SETUP.clear()
     adapm_amd.runtime._RUNTIME = None
-    V, D, N, B = 600, 48, 3, 24
+    V, N, B = 600, 3, 24
     adapm_amd.setup(num_keys=2 * V, num_threads=1, device="cuda:0")
     server = adapm_amd.Server(2 * D)
     worker = adapm_amd.Worker(0, server)

@@ -91,10 +91,10 @@ def _unique_batch(rng, E, R, B, N, pool=None):
     return s_k, r_k, o_k, n_k
 
 
-# 1. all unique: KPT 1 full block, partial block, KPT 2
-@pytest.mark.parametrize("D", [512, 64, 1024])
+# 1. all unique: KPT 1 full block, partial block, KPT 2, KPT 4, KPT 8
+@pytest.mark.parametrize("D", [512, 64, 1024, 2048, 4096])
 def test_all_unique(D):
-    E, R, B, N = 64, 8, 8, 3
+    E, R, B, N = (64, 8, 8, 3) if D <= 1024 else (32, 4, 4, 1)
     server, worker = _store(E + R, D)
     s_k, r_k, o_k, n_k = _unique_batch(np.random.default_rng(D), E, R, B, N)
     _check(server, worker, E + R, s_k, r_k, o_k, n_k, N, D, 0.05)

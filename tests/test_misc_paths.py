@@ -105,8 +105,9 @@ def test_techniques_aliases():
 
 
 def test_fused_step_guards_cpu():
-    """kge_step_fused must refuse a CPU store (it is the single-rank GPU
-    fast path; callers fall back to the classic pull/kernel/push path)."""
+    """The identity-path fused steps must refuse a CPU store (they are the
+    single-rank GPU fast path; callers fall back to the classic
+    pull/kernel/push path)."""
     import adapm_amd
 
     adapm_amd._SETUP.clear()
@@ -116,5 +117,9 @@ def test_fused_step_guards_cpu():
     k = torch.zeros(2, dtype=torch.int64)
     with pytest.raises(RuntimeError, match="GPU fast path"):
         s.raw.kge_step_fused(k, k, k, torch.zeros(4, dtype=torch.int64), 2, 4, 0.1, 1e-6)
+    with pytest.raises(RuntimeError, match="w2v_step_fused is the GPU fast path"):
+        s.raw.w2v_step_fused(k, k, torch.zeros(4, dtype=torch.int64), 2, 4, 0.1, 1e-6)
+    with pytest.raises(RuntimeError, match="mf_step_fused is the GPU fast path"):
+        s.raw.mf_step_fused(k, k, torch.zeros(2), 4, 0.1, 0.01, 1e-6)
     s.shutdown()
     adapm_amd._SETUP.clear()

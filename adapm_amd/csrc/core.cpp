@@ -3896,13 +3896,15 @@ torch::Tensor mf_loss(torch::Tensor w, torch::Tensor h, torch::Tensor x, int64_t
                       double lambda) {
   for (auto* t : {&w, &h, &x}) check_f32(*t, "mf loss tensor");
   int B = (int)x.numel();
-  auto out = torch::zeros({2}, torch::TensorOptions().dtype(torch::kFloat32).device(w.device()));
   if (w.is_cuda()) {
-    mf_loss_gpu(cfp(w), cfp(h), cfp(x), fp(out), B, (int)R, (float)lambda,
+    // summed in double on the device (see k_mf_loss), rounded once here
+    auto acc = torch::zeros({2}, torch::TensorOptions().dtype(torch::kFloat64).device(w.device()));
+    mf_loss_gpu(cfp(w), cfp(h), cfp(x), acc.data_ptr<double>(), B, (int)R, (float)lambda,
                 current_stream(w.device()));
-  } else {
-    mf_loss_cpu(cfp(w), cfp(h), cfp(x), fp(out), B, (int)R, (float)lambda);
+    return acc.to(torch::kFloat32);
   }
+  auto out = torch::zeros({2}, torch::TensorOptions().dtype(torch::kFloat32).device(w.device()));
+  mf_loss_cpu(cfp(w), cfp(h), cfp(x), fp(out), B, (int)R, (float)lambda);
   return out;
 }
 

@@ -142,8 +142,9 @@ void mf_update_step_cpu(const float* w, const float* h, const float* x, float* d
 
 // MF NZSL+L2 loss reduction over B nonzeros (reference apps/mf/loss.h:
 // 49-120: sum (x - w.h)^2 + lambda*(|w|^2 + |h|^2) per nonzero):
-// out[0] += squared-error sum, out[1] += regularizer sum.
-void mf_loss_gpu(const float* w, const float* h, const float* x, float* out2, int B, int R,
+// out[0] += squared-error sum, out[1] += regularizer sum. The device sums
+// are accumulated in double (acc2), which the caller rounds to fp32 once.
+void mf_loss_gpu(const float* w, const float* h, const float* x, double* acc2, int B, int R,
                  float lambda, void* stream);
 void mf_loss_cpu(const float* w, const float* h, const float* x, float* out2, int B, int R,
                  float lambda);

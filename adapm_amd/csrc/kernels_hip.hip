@@ -269,12 +269,16 @@ __global__ void k_mf_step(const float* __restrict__ w, const float* __restrict__
 
 // --------------------------------------------------------------- MF loss
 
+// The two sums are kept in double from the first sample on: up to 16384
+// workgroups add their share with one atomic each, in any order, and an fp32
+// sum of that many terms drifts by up to 2e-6 of the total, run to run. The
+// per-sample terms stay fp32.
 __global__ void k_mf_loss(const float* __restrict__ w, const float* __restrict__ h,
-                          const float* __restrict__ x, float* __restrict__ out2, int B, int R,
+                          const float* __restrict__ x, double* __restrict__ acc2, int B, int R,
                           float lambda) {
   __shared__ float lds[2][KT / 64];
   const int row = R << 1;
-  float se = 0.f, reg = 0.f;
+  double se = 0.0, reg = 0.0;
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     const float* wb = w + (int64_t)b * row;
     const float* hb = h + (int64_t)b * row;
@@ -288,21 +292,21 @@ __global__ void k_mf_loss(const float* __restrict__ w, const float* __restrict__
     float n2 = block_reduce_sum(nrm, lds[1]);
     if (threadIdx.x == 0) {
       float e = x[b] - pred;
-      se += e * e;
-      reg += lambda * n2;
+      se += (double)(e * e);
+      reg += (double)(lambda * n2);
     }
   }
   if (threadIdx.x == 0) {
-    atomicAdd(&out2[0], se);
-    atomicAdd(&out2[1], reg);
+    atomicAdd(&acc2[0], se);
+    atomicAdd(&acc2[1], reg);
   }
 }
 
-void mf_loss_gpu(const float* w, const float* h, const float* x, float* out2, int B, int R,
+void mf_loss_gpu(const float* w, const float* h, const float* x, double* acc2, int B, int R,
                  float lambda, void* stream) {
   if (B < 1) return;
   hipLaunchKernelGGL(k_mf_loss, dim3(grid_for(B)), dim3(KT), 0, (hipStream_t)stream, w, h, x,
-                     out2, B, R, lambda);
+                     acc2, B, R, lambda);
 }
 
 // --------------------------------------------------------------- alias draw

@@ -15,6 +15,8 @@ import dataclasses
 import numpy as np
 import torch
 
+from ._step import StepModel
+
 
 @dataclasses.dataclass
 class CTRConfig:
@@ -34,15 +36,9 @@ class CTRConfig:
         return 2 * self.dim
 
 
-class WideAndDeep:
+class WideAndDeep(StepModel):
     def __init__(self, cfg: CTRConfig, server, worker):
-        self.cfg = cfg
-        self.server = server
-        self.worker = worker
-        self.dev = server.rt.device
-        self.rank = server.rt.rank
-        self.world = server.rt.world
-        self.rng = np.random.default_rng(cfg.seed + self.rank)
+        super().__init__(cfg, server, worker)
         torch.manual_seed(cfg.seed)
         self.net = torch.nn.Sequential(
             torch.nn.Linear(cfg.fields * cfg.dim, cfg.hidden),
@@ -50,19 +46,11 @@ class WideAndDeep:
             torch.nn.Linear(cfg.hidden, 1),
         ).to(self.dev)
         self.opt = torch.optim.Adam(self.net.parameters(), lr=cfg.dense_lr)
-        self._pending = []
 
     def init_embeddings(self, scale=0.01):
         cfg = self.cfg
-        chunk = max(1, 2 ** 25 // cfg.row)
-        my_keys = np.arange(self.rank, cfg.num_features, self.world, dtype=np.int64)
-        for i in range(0, len(my_keys), chunk):
-            ks = my_keys[i:i + chunk]
-            vals = torch.zeros(len(ks), cfg.row, dtype=torch.float32, device=self.dev)
-            vals[:, :cfg.dim].normal_(0, scale)
-            self.worker.set(ks, vals)
-        self.worker.wait_sync()
-        self.worker.barrier()
+        self._init_owned(cfg.num_features, max(1, 2 ** 25 // cfg.row),
+                         lambda ks, vals: vals[:, :cfg.dim].normal_(0, scale))
 
     def signal_intent(self, feats, start, end=0):
         self.worker.intent(np.unique(feats.reshape(-1)), start, end)
@@ -108,17 +96,8 @@ class WideAndDeep:
         g2 = g * g
         delta[:, :cfg.dim] = -cfg.lr * g / torch.sqrt(accum + g2 + cfg.eps)
         delta[:, cfg.dim:] = g2
-        pt = w.push(keys_u, delta, async_=True)
-        if pt != -1:
-            self._pending.append(pt)
-        while len(self._pending) > 64:
-            w.wait(self._pending.pop(0))
-        return float(loss.item()) if sync_loss else loss
-
-    def drain(self):
-        for t in self._pending:
-            self.worker.wait(t)
-        self._pending.clear()
+        self._track(w.push(keys_u, delta, async_=True))
+        return self._loss_out(loss, sync_loss)
 
 
 def make_synthetic_ctr(n, num_features, fields, zipf_a=1.1, seed=0):

@@ -18,19 +18,18 @@ from __future__ import annotations
 
 import dataclasses
 import os
-import time
-from collections import defaultdict
 from typing import Optional
 
 import numpy as np
 import torch
 
-_PHASE_TIMING = os.environ.get("ADAPM_PHASE_TIMING", "0") == "1"
 # A/B switch: keep the host draw of the negatives on the fused world==1 path
 _HOST_NEGATIVES = os.environ.get("ADAPM_HOST_NEGATIVES", "0") == "1"
 
 import adapm_amd
 from adapm_amd import _C
+
+from ._step import StepModel
 
 
 @dataclasses.dataclass
@@ -55,44 +54,16 @@ class ComplExConfig:
         return 2 * self.dim
 
 
-class ComplEx:
-    def __init__(self, cfg: ComplExConfig, server: "adapm_amd.Server",
-                 worker: "adapm_amd.Worker"):
-        self.cfg = cfg
-        self.server = server
-        self.worker = worker
-        self.dev = server.rt.device
-        self.rank = server.rt.rank
-        self.world = server.rt.world
-        self.rng = np.random.default_rng(cfg.seed + self.rank)
-        self._pending = []
-        self._deferred = None  # fused-general: missed samples retried next step
-        self.phase_times = defaultdict(float)
-
-    def _ph(self, name, t0):
-        if _PHASE_TIMING:
-            if self.dev.type == "cuda":
-                torch.cuda.synchronize()
-            t = time.perf_counter()
-            self.phase_times[name] += t - t0
-            return t
-        return t0
-
+class ComplEx(StepModel):
     # ------------------------------------------------------------ init
 
     def init_embeddings(self):
         """Each rank initializes the keys it manages (key % world == rank)
         with set(); AdaGrad accumulators start at 0."""
         cfg = self.cfg
-        chunk = max(1, 2 ** 25 // cfg.row)  # ~128MB of values per set
-        my_keys = np.arange(self.rank, cfg.num_keys, self.world, dtype=np.int64)
-        for i in range(0, len(my_keys), chunk):
-            ks = my_keys[i:i + chunk]
-            vals = torch.zeros(len(ks), cfg.row, dtype=torch.float32, device=self.dev)
-            vals[:, :cfg.dim].normal_(0.0, cfg.init_scale)
-            self.worker.set(ks, vals)
-        self.worker.wait_sync()
-        self.worker.barrier()
+        self._init_owned(  # ~128MB of values per set
+            cfg.num_keys, max(1, 2 ** 25 // cfg.row),
+            lambda ks, vals: vals[:, :cfg.dim].normal_(0.0, cfg.init_scale))
 
     # ------------------------------------------------------------ train
 
@@ -107,71 +78,40 @@ class ComplEx:
         self.worker.intent(np.concatenate([s, r, o]), start, end)
 
     def _draw_negatives(self, B):
+        return self._negatives(B * self.cfg.neg_samples, self.cfg.num_entities)
+
+    def _launch(self, v, d, loss):
         cfg = self.cfg
-        w = self.worker
-        # negatives via the sampling manager (reference PrepareSample path)
-        if self.server.sampling is not None:
-            sid = w.prepare_sample(B * cfg.neg_samples, w.current_clock(),
-                                   w.current_clock() + 2)
-            neg_keys = self.server.sampling.pull(w, sid, B * cfg.neg_samples)
-            w.finish_sample(sid)
-        else:
-            neg_keys = self.rng.integers(0, cfg.num_entities, size=B * cfg.neg_samples,
-                                         dtype=np.int64)
-        return neg_keys
+        _C.kge_complex_step(*v, *d, loss, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
 
     def train_batch(self, triples: np.ndarray, async_push: bool = True,
                     sync_loss: bool = True, neg_keys: np.ndarray = None):
         """One training step over B positive triples. Returns mean loss
         (float if sync_loss else a device tensor, no host sync)."""
-        cfg = self.cfg
-        w = self.worker
-        B = len(triples)
-        t0 = time.perf_counter() if _PHASE_TIMING else 0.0
-        s_keys, r_keys, o_keys = self.keys_of(triples)
+        t0 = self._t0()
         if neg_keys is None:
-            neg_keys = self._draw_negatives(B)
+            neg_keys = self._draw_negatives(len(triples))
         t0 = self._ph("sample", t0)
+        handle = self._begin_step([*self.keys_of(triples), neg_keys])
+        return self._finish_step(handle, self._launch, sync_loss, t0,
+                                 wait_push=not async_push)
 
-        # one fused pull of all rows: [s | r | o | neg]
-        dev = self.dev
-        row = cfg.row
-        NN = B * cfg.neg_samples
-        all_keys = np.concatenate([s_keys, r_keys, o_keys, neg_keys])
-        all_v = torch.empty((3 * B + NN) * row, dtype=torch.float32, device=dev)
-        ts = w.pull(all_keys, all_v, async_=True)
-        w.wait(ts)
-        t0 = self._ph("pull", t0)
+    def _classic_step(self, arrays):
+        triples, negs2 = arrays
+        return self.train_batch(triples, sync_loss=False, neg_keys=negs2.reshape(-1))
 
-        s_v = all_v[: B * row].view(B, row)
-        r_v = all_v[B * row: 2 * B * row].view(B, row)
-        o_v = all_v[2 * B * row: 3 * B * row].view(B, row)
-        n_v = all_v[3 * B * row:].view(NN, row)
+    def _fused_identity_step(self, arrays):
+        return self._fused_raw(self.server.raw.kge_step_fused, arrays)
 
-        all_d = torch.empty_like(all_v)
-        ds = all_d[: B * row].view(B, row)
-        dr = all_d[B * row: 2 * B * row].view(B, row)
-        do = all_d[2 * B * row: 3 * B * row].view(B, row)
-        dn = all_d[3 * B * row:].view(NN, row)
-        loss = torch.empty(B, dtype=torch.float32, device=dev)
-        _C.kge_complex_step(s_v, r_v, o_v, n_v, ds, dr, do, dn, loss,
-                            cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
-        t0 = self._ph("kernel", t0)
+    def _fused_general_step(self, arrays):
+        return self._fused_raw(self.server.raw.kge_step_fused_general, arrays)
 
-        pt = w.push(all_keys, all_d, async_=True)
-        if pt != -1:
-            self._pending.append(pt)
-        if not async_push:
-            w.wait(pt)
-        # bounded async: cap outstanding pushes
-        while len(self._pending) > 64:
-            w.wait(self._pending.pop(0))
-        t0 = self._ph("push", t0)
-        if sync_loss:
-            out = float(loss.mean().item())
-            self._ph("loss_sync", t0)
-            return out
-        return loss
+    def _fused_raw(self, step, arrays):
+        cfg = self.cfg
+        triples, negs2 = arrays
+        return step(*map(torch.from_numpy, self.keys_of(triples)),
+                    torch.from_numpy(np.ascontiguousarray(negs2.reshape(-1))),
+                    cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
 
     def train_batch_fused(self, triples: np.ndarray, sync_loss: bool = False,
                           force_general: bool = False):
@@ -186,15 +126,10 @@ class ComplEx:
         enables the general path on the CPU store (the gloo test tier)."""
         cfg = self.cfg
         w = self.worker
-        raw = self.server.raw
-        if self.dev.type != "cuda" and not force_general:
-            return self.train_batch(triples, sync_loss=sync_loss)
         B = len(triples)
-        s_keys, r_keys, o_keys = self.keys_of(triples)
-
-        fast = self.world == 1 and not force_general and raw.layout_identity()
         smp = self.server.sampling
-        if fast and smp is not None and not _HOST_NEGATIVES and smp.device_stream() is not None:
+        if (smp is not None and not _HOST_NEGATIVES and self._fused_identity(force_general)
+                and smp.device_stream() is not None):
             # negatives drawn on the device inside the step: the same keys
             # the host draw would give (ADAPM_HOST_NEGATIVES=1 keeps that
             # draw, for A/B runs)
@@ -202,67 +137,13 @@ class ComplEx:
             sid = w.prepare_sample(NN, w.current_clock(), w.current_clock() + 2)
             us = smp.pull_device(w, sid, NN, draw=False)
             w.finish_sample(sid)
-            loss, _neg = raw.kge_step_fused_sampled(
-                torch.from_numpy(s_keys), torch.from_numpy(r_keys), torch.from_numpy(o_keys),
+            loss, _neg = self.server.raw.kge_step_fused_sampled(
+                *map(torch.from_numpy, self.keys_of(triples)),
                 us, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
-            return float(loss.mean().item()) if sync_loss else loss
-
-        neg_keys = np.ascontiguousarray(self._draw_negatives(B), dtype=np.int64)
-
-        if fast:
-            loss = raw.kge_step_fused(
-                torch.from_numpy(s_keys), torch.from_numpy(r_keys), torch.from_numpy(o_keys),
-                torch.from_numpy(neg_keys), cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
-            return float(loss.mean().item()) if sync_loss else loss
-
-        # Missed (any-key-remote) samples would block THIS step on a
-        # sync round-trip through the classic path. Intent was signaled
-        # `lookahead` steps ago, so a miss is usually a straggler whose
-        # replica lands within a round — DEFER it one step and retry
-        # fused (second miss goes classic immediately, so nothing starves).
-        negs2 = neg_keys.reshape(B, cfg.neg_samples)
-        if self._deferred is not None:
-            dtr, dng = self._deferred
-            self._deferred = None
-            n_def = len(dtr)
-            triples = np.concatenate([dtr, triples])
-            negs2 = np.concatenate([dng, negs2])
-            s_keys, r_keys, o_keys = self.keys_of(triples)
-            neg_keys = negs2.reshape(-1)
-        else:
-            n_def = 0
-
-        loss, missed = raw.kge_step_fused_general(
-            torch.from_numpy(s_keys), torch.from_numpy(r_keys), torch.from_numpy(o_keys),
-            torch.from_numpy(np.ascontiguousarray(neg_keys)), cfg.neg_samples, cfg.dim,
-            cfg.lr, cfg.eps)
-        if missed.numel() == 0:
-            return float(loss.mean().item()) if sync_loss else loss
-        midx = missed.numpy()
-        old = midx[midx < n_def]      # second miss: classic now
-        fresh = midx[midx >= n_def]   # first miss: retry fused next step
-        if len(fresh):
-            self._deferred = (triples[fresh], negs2[fresh])
-        if len(old):
-            mloss = self.train_batch(triples[old], sync_loss=False,
-                                     neg_keys=negs2[old].reshape(-1))
-            if not torch.is_tensor(mloss):
-                mloss = torch.tensor([mloss])
-            loss = torch.cat([loss, mloss.to(loss.device)])
-        if loss.numel() == 0:
-            return 0.0 if sync_loss else loss
-        return float(loss.mean().item()) if sync_loss else loss
-
-    def drain(self):
-        if self._deferred is not None:
-            # flush straggler samples through the classic path so an
-            # epoch boundary never drops work
-            dtr, dng = self._deferred
-            self._deferred = None
-            self.train_batch(dtr, sync_loss=False, neg_keys=dng.reshape(-1))
-        for t in self._pending:
-            self.worker.wait(t)
-        self._pending.clear()
+            return self._loss_out(loss, sync_loss)
+        negs2 = np.ascontiguousarray(self._draw_negatives(B), dtype=np.int64)
+        return self._fused_step((triples, negs2.reshape(B, cfg.neg_samples)),
+                                sync_loss, force_general)
 
     # ---------------------------------------------- prefetch pipeline
 
@@ -271,49 +152,13 @@ class ComplEx:
         reference's max_concurrent_loops pipelining): sample negatives,
         allocate buffers, issue one async pull. Returns a handle for
         train_prefetched."""
-        cfg = self.cfg
-        w = self.worker
-        B = len(triples)
-        s_keys, r_keys, o_keys = self.keys_of(triples)
-        if self.server.sampling is not None:
-            sid = w.prepare_sample(B * cfg.neg_samples, w.current_clock(),
-                                   w.current_clock() + 2)
-            neg_keys = self.server.sampling.pull(w, sid, B * cfg.neg_samples)
-            w.finish_sample(sid)
-        else:
-            neg_keys = self.rng.integers(0, cfg.num_entities, size=B * cfg.neg_samples,
-                                         dtype=np.int64)
-        all_keys = np.concatenate([s_keys, r_keys, o_keys, neg_keys])
-        all_v = torch.empty(len(all_keys) * cfg.row, dtype=torch.float32, device=self.dev)
-        ts = w.pull(all_keys, all_v, async_=True)
-        return (B, all_keys, all_v, ts)
+        return self._begin_step([*self.keys_of(triples),
+                                 self._draw_negatives(len(triples))])
 
     def train_prefetched(self, handle, sync_loss: bool = False):
-        """Finish a prefetched batch: wait for the pull, run the fused
+        """Finish a prefetched batch: wait for the pull, run the step
         kernel, push the deltas."""
-        cfg = self.cfg
-        w = self.worker
-        B, all_keys, all_v, ts = handle
-        w.wait(ts)
-        row = cfg.row
-        NN = B * cfg.neg_samples
-        s_v = all_v[: B * row].view(B, row)
-        r_v = all_v[B * row: 2 * B * row].view(B, row)
-        o_v = all_v[2 * B * row: 3 * B * row].view(B, row)
-        n_v = all_v[3 * B * row:].view(NN, row)
-        all_d = torch.empty_like(all_v)
-        loss = torch.empty(B, dtype=torch.float32, device=self.dev)
-        _C.kge_complex_step(s_v, r_v, o_v, n_v, all_d[: B * row].view(B, row),
-                            all_d[B * row: 2 * B * row].view(B, row),
-                            all_d[2 * B * row: 3 * B * row].view(B, row),
-                            all_d[3 * B * row:].view(NN, row), loss,
-                            cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
-        pt = w.push(all_keys, all_d, async_=True)
-        if pt != -1:
-            self._pending.append(pt)
-        while len(self._pending) > 64:
-            w.wait(self._pending.pop(0))
-        return float(loss.mean().item()) if sync_loss else loss
+        return self._finish_step(handle, self._launch, sync_loss)
 
     # ------------------------------------------------------------ eval
 
@@ -566,21 +411,12 @@ if __name__ == "__main__":
     main()
 
 
-class Rescal:
+class Rescal(StepModel):
     """RESCAL scorer (reference knowledge_graph_embeddings.cc:895-922):
     psi = e_s^T R e_o with a D x D matrix per relation. Exercises the
     store's NON-UNIFORM value lengths: entity rows 2*D floats, relation
-    rows 2*D*D floats."""
-
-    def __init__(self, cfg: ComplExConfig, server, worker):
-        self.cfg = cfg
-        self.server = server
-        self.worker = worker
-        self.dev = server.rt.device
-        self.rank = server.rt.rank
-        self.world = server.rt.world
-        self.rng = np.random.default_rng(cfg.seed + self.rank)
-        self._pending = []
+    rows 2*D*D floats, so it pulls and pushes role by role instead of
+    taking the skeleton's one-buffer classic step."""
 
     @staticmethod
     def value_lengths(num_entities, num_relations, dim):
@@ -633,13 +469,7 @@ class Rescal:
         s_keys = triples[:, 0].astype(np.int64)
         r_keys = (cfg.num_entities + triples[:, 1]).astype(np.int64)
         o_keys = triples[:, 2].astype(np.int64)
-        if self.server.sampling is not None:
-            sid = w.prepare_sample(B * cfg.neg_samples, w.current_clock(), w.current_clock() + 2)
-            neg_keys = self.server.sampling.pull(w, sid, B * cfg.neg_samples)
-            w.finish_sample(sid)
-        else:
-            neg_keys = self.rng.integers(0, cfg.num_entities, size=B * cfg.neg_samples,
-                                         dtype=np.int64)
+        neg_keys = self._negatives(B * cfg.neg_samples, cfg.num_entities)
         opts = dict(dtype=torch.float32, device=self.dev)
         s_v = torch.empty(B, 2 * D, **opts)
         o_v = torch.empty(B, 2 * D, **opts)
@@ -667,14 +497,5 @@ class Rescal:
                            cfg.neg_samples, D, cfg.lr, cfg.eps)
             push_sets = ((s_keys, ds), (r_keys, drl), (o_keys, do), (neg_keys, dn))
         for kt, dt in push_sets:
-            pt = w.push(kt, dt, async_=True)
-            if pt != -1:
-                self._pending.append(pt)
-        while len(self._pending) > 64:
-            w.wait(self._pending.pop(0))
-        return float(loss.mean().item()) if sync_loss else loss
-
-    def drain(self):
-        for t in self._pending:
-            self.worker.wait(t)
-        self._pending.clear()
+            self._track(w.push(kt, dt, async_=True))
+        return self._loss_out(loss, sync_loss)

@@ -22,6 +22,8 @@ import torch
 
 from adapm_amd import _C
 
+from ._step import StepModel
+
 
 @dataclasses.dataclass
 class MFConfig:
@@ -45,58 +47,50 @@ class MFConfig:
         return 2 * self.rank
 
 
-class MF:
-    def __init__(self, cfg: MFConfig, server, worker):
-        self.cfg = cfg
-        self.server = server
-        self.worker = worker
-        self.dev = server.rt.device
-        self.rank_id = server.rt.rank
-        self.world = server.rt.world
-        self.rng = np.random.default_rng(cfg.seed + self.rank_id)
-        self._pending = []
-        self._deferred = None  # fused-general: missed nonzeros retried next step
+class MF(StepModel):
+    @property
+    def rank_id(self):
+        """The process rank (cfg.rank is the factorization rank)."""
+        return self.rank
 
     def col_key(self, j):
         return self.cfg.num_rows + np.asarray(j, dtype=np.int64)
 
     def init_factors(self, scale=0.1):
         cfg = self.cfg
-        chunk = max(1, 2 ** 25 // cfg.row)
-        my_keys = np.arange(self.rank_id, cfg.num_keys, self.world, dtype=np.int64)
-        for i in range(0, len(my_keys), chunk):
-            ks = my_keys[i:i + chunk]
-            vals = torch.zeros(len(ks), cfg.row, dtype=torch.float32, device=self.dev)
+
+        def fill(ks, vals):
             vals[:, :cfg.rank].uniform_(0, scale)
             vals[:, cfg.rank:] = cfg.accum_init
-            self.worker.set(ks, vals)
-        self.worker.wait_sync()
-        self.worker.barrier()
+
+        self._init_owned(cfg.num_keys, max(1, 2 ** 25 // cfg.row), fill)
 
     def train_batch(self, rows, cols, ratings, sync_loss=False):
         cfg = self.cfg
-        w = self.worker
-        B = len(rows)
-        k_w = np.asarray(rows, dtype=np.int64)
-        k_h = self.col_key(cols)
-        all_keys = np.concatenate([k_w, k_h])
-        row = cfg.row
-        all_v = torch.empty(2 * B * row, dtype=torch.float32, device=self.dev)
-        w.wait(w.pull(all_keys, all_v, async_=True))
-        w_v = all_v[:B * row].view(B, row)
-        h_v = all_v[B * row:].view(B, row)
+        t0 = self._t0()
+        # one pull of all rows: [w | h]
+        handle = self._begin_step([np.asarray(rows, dtype=np.int64), self.col_key(cols)])
         x = torch.as_tensor(np.asarray(ratings, dtype=np.float32), device=self.dev)
-        all_d = torch.empty_like(all_v)
-        dw = all_d[:B * row].view(B, row)
-        dh = all_d[B * row:].view(B, row)
-        loss = torch.empty(B, dtype=torch.float32, device=self.dev)
-        _C.mf_update_step(w_v, h_v, x, dw, dh, loss, cfg.rank, cfg.lr, cfg.lam, cfg.eps)
-        pt = w.push(all_keys, all_d, async_=True)
-        if pt != -1:
-            self._pending.append(pt)
-        while len(self._pending) > 64:
-            w.wait(self._pending.pop(0))
-        return float(loss.mean().item()) if sync_loss else loss
+
+        def launch(v, d, loss):
+            _C.mf_update_step(*v, x, *d, loss, cfg.rank, cfg.lr, cfg.lam, cfg.eps)
+
+        return self._finish_step(handle, launch, sync_loss, t0)
+
+    def _classic_step(self, arrays):
+        return self.train_batch(*arrays, sync_loss=False)
+
+    def _fused_identity_step(self, arrays):
+        return self._fused_raw(self.server.raw.mf_step_fused, arrays)
+
+    def _fused_general_step(self, arrays):
+        return self._fused_raw(self.server.raw.mf_step_fused_general, arrays)
+
+    def _fused_raw(self, step, arrays):
+        cfg = self.cfg
+        rows, cols, ratings = arrays
+        return step(torch.from_numpy(rows), torch.from_numpy(self.col_key(cols)),
+                    torch.from_numpy(ratings), cfg.rank, cfg.lr, cfg.lam, cfg.eps)
 
     def train_batch_fused(self, rows, cols, ratings, sync_loss=False,
                           force_general=False):
@@ -104,58 +98,9 @@ class MF:
         zero-host-work kernel (Server.mf_step_fused); otherwise the
         general offsets path runs the fused kernel on all-local nonzeros
         and routes the remote remainder through the classic path."""
-        cfg = self.cfg
-        raw = self.server.raw
-        if self.dev.type != "cuda" and not force_general:
-            return self.train_batch(rows, cols, ratings, sync_loss=sync_loss)
-        k_w = torch.from_numpy(np.asarray(rows, dtype=np.int64))
-        k_h = torch.from_numpy(self.col_key(cols))
-        x = torch.from_numpy(np.asarray(ratings, dtype=np.float32))
-        if self.world == 1 and not force_general and raw.layout_identity():
-            loss = raw.mf_step_fused(k_w, k_h, x, cfg.rank, cfg.lr, cfg.lam, cfg.eps)
-            return float(loss.mean().item()) if sync_loss else loss
-        # defer first-time misses one step (intent usually localizes
-        # them within a round); a second miss goes classic immediately
-        rows = np.asarray(rows, dtype=np.int64)
-        cols = np.asarray(cols, dtype=np.int64)
-        ratings = np.asarray(ratings, dtype=np.float32)
-        n_def = 0
-        if self._deferred is not None:
-            dr, dcs, drt = self._deferred
-            self._deferred = None
-            n_def = len(dr)
-            rows = np.concatenate([dr, rows])
-            cols = np.concatenate([dcs, cols])
-            ratings = np.concatenate([drt, ratings])
-            k_w = torch.from_numpy(rows)
-            k_h = torch.from_numpy(self.col_key(cols))
-            x = torch.from_numpy(ratings)
-        loss, missed = raw.mf_step_fused_general(k_w, k_h, x, cfg.rank, cfg.lr, cfg.lam,
-                                                 cfg.eps)
-        if missed.numel():
-            midx = missed.numpy()
-            old_i = midx[midx < n_def]
-            fresh = midx[midx >= n_def]
-            if len(fresh):
-                self._deferred = (rows[fresh], cols[fresh], ratings[fresh])
-            if len(old_i):
-                mloss = self.train_batch(rows[old_i], cols[old_i], ratings[old_i],
-                                         sync_loss=False)
-                if not torch.is_tensor(mloss):
-                    mloss = torch.tensor([mloss])
-                loss = torch.cat([loss, mloss.to(loss.device)])
-        if loss.numel() == 0:
-            return 0.0 if sync_loss else loss
-        return float(loss.mean().item()) if sync_loss else loss
-
-    def drain(self):
-        if self._deferred is not None:
-            dr, dcs, drt = self._deferred
-            self._deferred = None
-            self.train_batch(dr, dcs, drt, sync_loss=False)
-        for t in self._pending:
-            self.worker.wait(t)
-        self._pending.clear()
+        arrays = (np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64),
+                  np.asarray(ratings, dtype=np.float32))
+        return self._fused_step(arrays, sync_loss, force_general)
 
     # -------------------------------------------------- schedules
 

@@ -21,6 +21,8 @@ import torch
 import adapm_amd
 from adapm_amd import _C
 
+from ._step import StepModel
+
 
 @dataclasses.dataclass
 class W2VConfig:
@@ -53,35 +55,23 @@ def syn1(words):
     return 2 * np.asarray(words, dtype=np.int64) + 1
 
 
-class Word2Vec:
+class Word2Vec(StepModel):
     def __init__(self, cfg: W2VConfig, server, worker):
-        self.cfg = cfg
-        self.server = server
-        self.worker = worker
-        self.dev = server.rt.device
-        self.rank = server.rt.rank
-        self.world = server.rt.world
-        self.rng = np.random.default_rng(cfg.seed + self.rank)
-        self._pending = []
-        self._deferred = None  # fused-general: missed pairs retried next step
+        super().__init__(cfg, server, worker)
         self._keep_prob = None
         self.words = None  # real-corpus vocab strings (data_io.build_vocab)
 
     def init_embeddings(self):
         cfg = self.cfg
-        chunk = max(1, 2 ** 25 // cfg.row)
-        my_keys = np.arange(self.rank, cfg.num_keys, self.world, dtype=np.int64)
-        for i in range(0, len(my_keys), chunk):
-            ks = my_keys[i:i + chunk]
-            vals = torch.zeros(len(ks), cfg.row, dtype=torch.float32, device=self.dev)
+
+        def fill(ks, vals):
             # syn0 random-uniform (reference: (rand-0.5)/dim), syn1 zero
             mask = torch.from_numpy((ks % 2 == 0)).to(self.dev)
             vals[:, :cfg.dim] = (torch.rand(len(ks), cfg.dim, device=self.dev) - 0.5) / cfg.dim
             vals[~mask, :cfg.dim] = 0.0
             vals[:, cfg.dim:] = cfg.accum_init
-            self.worker.set(ks, vals)
-        self.worker.wait_sync()
-        self.worker.barrier()
+
+        self._init_owned(cfg.num_keys, max(1, 2 ** 25 // cfg.row), fill)
 
     def set_vocab_counts(self, counts, sample: float = 1e-3):
         """Frequent-word subsampling (reference word2vec.cc 'sample'
@@ -113,40 +103,36 @@ class Word2Vec:
         words = np.unique(np.concatenate([np.asarray(s, dtype=np.int64) for s in sentences]))
         self.worker.intent(np.concatenate([syn0(words), syn1(words)]), start, end)
 
-    def train_pairs(self, ctr_words, ctx_words, sync_loss=False, neg_words=None):
+    def _launch(self, v, d, loss):
         cfg = self.cfg
-        w = self.worker
-        B = len(ctr_words)
-        if neg_words is None:
-            if self.server.sampling is not None:
-                sid = w.prepare_sample(B * cfg.negative, w.current_clock(),
-                                       w.current_clock() + 2)
-                neg_words = self.server.sampling.pull(w, sid, B * cfg.negative)
-                w.finish_sample(sid)
-            else:
-                neg_words = self.rng.integers(0, cfg.vocab_size, size=B * cfg.negative)
+        _C.w2v_sgns_step(*v, *d, loss, cfg.negative, cfg.dim, cfg.lr, cfg.eps)
 
-        k_ctr, k_ctx, k_neg = syn0(ctr_words), syn1(ctx_words), syn1(neg_words)
-        all_keys = np.concatenate([k_ctr, k_ctx, k_neg])
-        row = cfg.row
-        all_v = torch.empty(len(all_keys) * row, dtype=torch.float32, device=self.dev)
-        w.wait(w.pull(all_keys, all_v, async_=True))
-        c_v = all_v[:B * row].view(B, row)
-        x_v = all_v[B * row:2 * B * row].view(B, row)
-        n_v = all_v[2 * B * row:].view(B * cfg.negative, row)
-        all_d = torch.empty_like(all_v)
-        dc = all_d[:B * row].view(B, row)
-        dx = all_d[B * row:2 * B * row].view(B, row)
-        dn = all_d[2 * B * row:].view(B * cfg.negative, row)
-        loss = torch.empty(B, dtype=torch.float32, device=self.dev)
-        _C.w2v_sgns_step(c_v, x_v, n_v, dc, dx, dn, loss, cfg.negative, cfg.dim,
-                         cfg.lr, cfg.eps)
-        pt = w.push(all_keys, all_d, async_=True)
-        if pt != -1:
-            self._pending.append(pt)
-        while len(self._pending) > 64:
-            w.wait(self._pending.pop(0))
-        return float(loss.mean().item()) if sync_loss else loss
+    def train_pairs(self, ctr_words, ctx_words, sync_loss=False, neg_words=None):
+        t0 = self._t0()
+        if neg_words is None:
+            neg_words = self._negatives(len(ctr_words) * self.cfg.negative,
+                                        self.cfg.vocab_size)
+        t0 = self._ph("sample", t0)
+        # one pull of all rows: [ctr | ctx | neg]
+        handle = self._begin_step([syn0(ctr_words), syn1(ctx_words), syn1(neg_words)])
+        return self._finish_step(handle, self._launch, sync_loss, t0)
+
+    def _classic_step(self, arrays):
+        ctr, ctx, negs2 = arrays
+        return self.train_pairs(ctr, ctx, sync_loss=False, neg_words=negs2.reshape(-1))
+
+    def _fused_identity_step(self, arrays):
+        return self._fused_raw(self.server.raw.w2v_step_fused, arrays)
+
+    def _fused_general_step(self, arrays):
+        return self._fused_raw(self.server.raw.w2v_step_fused_general, arrays)
+
+    def _fused_raw(self, step, arrays):
+        cfg = self.cfg
+        ctr, ctx, negs2 = arrays
+        return step(torch.from_numpy(syn0(ctr)), torch.from_numpy(syn1(ctx)),
+                    torch.from_numpy(syn1(negs2.reshape(-1))),
+                    cfg.negative, cfg.dim, cfg.lr, cfg.eps)
 
     def train_pairs_fused(self, ctr_words, ctx_words, sync_loss=False,
                           force_general=False):
@@ -155,64 +141,12 @@ class Word2Vec:
         general offsets path runs the fused kernel on all-local pairs
         and routes the remote remainder through the classic path."""
         cfg = self.cfg
-        w = self.worker
-        raw = self.server.raw
-        if self.dev.type != "cuda" and not force_general:
-            return self.train_pairs(ctr_words, ctx_words, sync_loss=sync_loss)
         B = len(ctr_words)
-        if self.server.sampling is not None:
-            sid = w.prepare_sample(B * cfg.negative, w.current_clock(), w.current_clock() + 2)
-            neg_words = self.server.sampling.pull(w, sid, B * cfg.negative)
-            w.finish_sample(sid)
-        else:
-            neg_words = self.rng.integers(0, cfg.vocab_size, size=B * cfg.negative)
-        neg_words = np.ascontiguousarray(neg_words, dtype=np.int64)
-        if self.world == 1 and not force_general and raw.layout_identity():
-            loss = raw.w2v_step_fused(
-                torch.from_numpy(syn0(ctr_words)), torch.from_numpy(syn1(ctx_words)),
-                torch.from_numpy(syn1(neg_words)), cfg.negative, cfg.dim, cfg.lr, cfg.eps)
-            return float(loss.mean().item()) if sync_loss else loss
-        # defer first-time misses one step (intent usually localizes them
-        # within a round); a second miss goes classic immediately
-        ctr_words = np.asarray(ctr_words, dtype=np.int64)
-        ctx_words = np.asarray(ctx_words, dtype=np.int64)
-        negs2 = neg_words.reshape(B, cfg.negative)
-        n_def = 0
-        if self._deferred is not None:
-            dc, dx, dn = self._deferred
-            self._deferred = None
-            n_def = len(dc)
-            ctr_words = np.concatenate([dc, ctr_words])
-            ctx_words = np.concatenate([dx, ctx_words])
-            negs2 = np.concatenate([dn, negs2])
-        loss, missed = raw.w2v_step_fused_general(
-            torch.from_numpy(syn0(ctr_words)), torch.from_numpy(syn1(ctx_words)),
-            torch.from_numpy(syn1(np.ascontiguousarray(negs2.reshape(-1)))),
-            cfg.negative, cfg.dim, cfg.lr, cfg.eps)
-        if missed.numel():
-            midx = missed.numpy()
-            old = midx[midx < n_def]
-            fresh = midx[midx >= n_def]
-            if len(fresh):
-                self._deferred = (ctr_words[fresh], ctx_words[fresh], negs2[fresh])
-            if len(old):
-                mloss = self.train_pairs(ctr_words[old], ctx_words[old], sync_loss=False,
-                                         neg_words=negs2[old].reshape(-1))
-                if not torch.is_tensor(mloss):
-                    mloss = torch.tensor([mloss])
-                loss = torch.cat([loss, mloss.to(loss.device)])
-        if loss.numel() == 0:
-            return 0.0 if sync_loss else loss
-        return float(loss.mean().item()) if sync_loss else loss
-
-    def drain(self):
-        if self._deferred is not None:
-            dc, dx, dn = self._deferred
-            self._deferred = None
-            self.train_pairs(dc, dx, sync_loss=False, neg_words=dn.reshape(-1))
-        for t in self._pending:
-            self.worker.wait(t)
-        self._pending.clear()
+        neg_words = np.ascontiguousarray(self._negatives(B * cfg.negative, cfg.vocab_size),
+                                         dtype=np.int64)
+        arrays = (np.asarray(ctr_words, dtype=np.int64), np.asarray(ctx_words, dtype=np.int64),
+                  neg_words.reshape(B, cfg.negative))
+        return self._fused_step(arrays, sync_loss, force_general)
 
     def export_text(self, path: str, max_words: int = None, chunk: int = 65536):
         """word2vec text format: '<vocab> <dim>' header then word vectors

@@ -67,6 +67,7 @@ extern "C" {
 int adapm_host_arena_alloc(long long floats, int want_device_visible, void** host_ptr,
                            void** dev_ptr);
 void adapm_host_arena_free(void* host_ptr, int was_device_visible);
+int adapm_host_device_ptr(void* host_ptr, void** dev_ptr);
 }
 
 namespace adapm {
@@ -805,10 +806,12 @@ class Server {
   void run_scatter_keys(const torch::Tensor& keys_cpu, const torch::Tensor& in, bool set) {
     if (dev_.is_cuda()) {
       auto kd = keys_cpu.to(dev_, /*non_blocking=*/true);
-      // NOTE: a sorted chunked scatter (ops_scatter_sorted_gpu) was
-      // measured here and LOST to plain HW atomics on every workload
-      // (the device sort + permuted reads cost more than hot-row atomic
-      // contention saves) — keep the straightforward atomic path.
+      // NOTE: a sorted chunked scatter (device sort of the keys, then
+      // consecutive duplicates pre-summed in registers, one atomic per
+      // 16-row chunk) was measured here and LOST to plain HW atomics on
+      // every workload (the device sort + permuted reads cost more than
+      // hot-row atomic contention saves). It has been removed — keep the
+      // straightforward atomic path.
       ops_scatter_keys_gpu(slab_.bases(), key_batch(kd), in.data_ptr<float>(), set,
                            current_stream(dev_));
     } else {
@@ -3923,6 +3926,159 @@ torch::Tensor alias_draw(torch::Tensor prob, torch::Tensor alias, int64_t seed, 
   return out;
 }
 
+// ---- test-only entries into the slab ops (tests/test_slab_ops.py) ----
+// Plumbing and nothing else: check that every range the batch names lies
+// inside its tensor, upload the batch, and hand it to the *_gpu or *_cpu
+// function on the current stream. No production path calls these.
+
+static void check_slab_tensor(const torch::Tensor& t, torch::ScalarType st, const char* name) {
+  TORCH_CHECK(t.is_contiguous() && t.scalar_type() == st, name, ": wrong dtype or not contiguous");
+  // the float4 paths test offsets only; the base has to be aligned itself
+  TORCH_CHECK(((uintptr_t)t.data_ptr() & 15) == 0, name, ": base must be 16-byte aligned");
+}
+
+static void check_host_batch_tensor(const torch::Tensor& t, torch::ScalarType st, int64_t n,
+                                    const char* name) {
+  TORCH_CHECK(t.device().is_cpu() && t.is_contiguous() && t.scalar_type() == st && t.dim() == 1,
+              name, ": expected a contiguous 1-d CPU tensor of the batch dtype");
+  TORCH_CHECK(t.numel() == n, name, ": ", t.numel(), " entries, batch has ", n);
+}
+
+// device-side base of the arena: the tensor's own pointer on the CPU, the
+// device-visible alias of a pinned tensor on the GPU
+static float* arena_base(const c10::optional<torch::Tensor>& host, bool gpu) {
+  if (!host.has_value()) return nullptr;
+  const torch::Tensor& h = *host;
+  TORCH_CHECK(h.device().is_cpu(), "host arena must be a CPU tensor");
+  check_slab_tensor(h, torch::kFloat32, "host arena");
+  if (!gpu) return h.data_ptr<float>();
+  void* d = nullptr;
+  TORCH_CHECK(h.numel() > 0 && h.is_pinned() && adapm_host_device_ptr(h.data_ptr(), &d) == 0,
+              "host arena is not device-visible (pin it)");
+  return (float*)d;
+}
+
+void slab_op(const std::string& op, torch::Tensor dev, c10::optional<torch::Tensor> host,
+             torch::Tensor src_off, torch::Tensor dst_off, torch::Tensor lens,
+             c10::optional<torch::Tensor> aux_off, c10::optional<torch::Tensor> buf, bool set) {
+  enum { GATHER, SCATTER, RMW, EXTRACT, REFRESH, ZERO, SQNORM } kind = GATHER;
+  if (op == "gather") kind = GATHER;
+  else if (op == "scatter") kind = SCATTER;
+  else if (op == "scatter_rmw") kind = RMW;
+  else if (op == "extract") kind = EXTRACT;
+  else if (op == "refresh") kind = REFRESH;
+  else if (op == "zero") kind = ZERO;
+  else if (op == "delta_sqnorm") kind = SQNORM;
+  else TORCH_CHECK(false, "slab_op: unknown op '", op, "'");
+  const bool gpu = dev.is_cuda();
+  const bool has_aux = kind == EXTRACT || kind == REFRESH || kind == SQNORM;
+  const bool has_buf = kind != ZERO;
+  TORCH_CHECK(set == false || kind == SCATTER, "slab_op: set applies to scatter only");
+  TORCH_CHECK(gpu || kind != RMW, "slab_op: scatter_rmw has no CPU backend");
+  TORCH_CHECK(!gpu || hip_available(), "slab_op: CUDA tensor but no HIP device");
+  check_slab_tensor(dev, torch::kFloat32, "dev slab");
+  SlabBases sb{dev.data_ptr<float>(), arena_base(host, gpu)};
+  const int64_t dev_n = dev.numel(), host_n = host.has_value() ? host->numel() : 0;
+
+  const int64_t n = src_off.numel();
+  TORCH_CHECK(n <= std::numeric_limits<int>::max(), "slab_op: batch too large");
+  check_host_batch_tensor(src_off, torch::kInt64, n, "src_off");
+  check_host_batch_tensor(dst_off, torch::kInt64, n, "dst_off");
+  check_host_batch_tensor(lens, torch::kInt32, n, "lens");
+  TORCH_CHECK(aux_off.has_value() == has_aux, "slab_op: aux_off goes with extract, refresh and "
+                                              "delta_sqnorm only");
+  if (has_aux) check_host_batch_tensor(*aux_off, torch::kInt64, n, "aux_off");
+  TORCH_CHECK(buf.has_value() == has_buf, "slab_op: every op but zero takes a buffer");
+  int64_t buf_n = 0;
+  if (has_buf) {
+    check_slab_tensor(*buf, torch::kFloat32, "buf");
+    TORCH_CHECK(buf->device() == dev.device(), "slab_op: buf and dev on different devices");
+    buf_n = buf->numel();
+  }
+
+  // zero names its slab rows in dst_off (as Server::run_zero does); every
+  // other op names them in src_off and a buffer range in dst_off
+  const int64_t* so = (kind == ZERO ? dst_off : src_off).data_ptr<int64_t>();
+  const int64_t* bo = dst_off.data_ptr<int64_t>();
+  const int64_t* ao = has_aux ? aux_off->data_ptr<int64_t>() : nullptr;
+  const int32_t* ln = lens.data_ptr<int32_t>();
+  auto in_slab = [&](int64_t off, int64_t len, int64_t i, const char* what) {
+    TORCH_CHECK(off >= 0, "slab_op: ", what, "[", i, "] is negative");
+    const bool spilled = (off & SPILL_BIT) != 0;
+    TORCH_CHECK(!spilled || sb.host, "slab_op: ", what, "[", i, "] is spilled, no arena given");
+    const int64_t o = off & ~SPILL_BIT, cap = spilled ? host_n : dev_n;
+    TORCH_CHECK(o <= cap && len <= cap - o, "slab_op: ", what, "[", i, "] = ", o, " + ", len,
+                " floats leaves its ", spilled ? "arena" : "slab", " of ", cap);
+  };
+  for (int64_t i = 0; i < n; ++i) {
+    TORCH_CHECK(ln[i] >= 0, "slab_op: lens[", i, "] is negative");
+    if (so[i] < 0) {
+      TORCH_CHECK(so[i] == -1, "slab_op: a skip is written -1");
+      continue;
+    }
+    in_slab(so[i], ln[i], i, "slab offset");
+    if (has_aux) in_slab(ao[i], ln[i], i, "aux_off");
+    if (has_buf) {
+      const int64_t bl = kind == SQNORM ? 1 : ln[i];
+      TORCH_CHECK(bo[i] >= 0 && bo[i] <= buf_n && bl <= buf_n - bo[i], "slab_op: dst_off[", i,
+                  "] = ", bo[i], " + ", bl, " floats leaves the buffer of ", buf_n);
+    }
+  }
+
+  auto up = [&](const torch::Tensor& t) { return gpu ? t.to(dev.device()) : t; };
+  torch::Tensor s_d = up(src_off), d_d = up(dst_off), l_d = up(lens), a_d;
+  if (has_aux) a_d = up(*aux_off);
+  OpsBatch b{s_d.data_ptr<int64_t>(), d_d.data_ptr<int64_t>(), l_d.data_ptr<int32_t>(), (int)n};
+  const int64_t* a = has_aux ? a_d.data_ptr<int64_t>() : nullptr;
+  float* bp = has_buf ? buf->data_ptr<float>() : nullptr;
+  void* st = current_stream(dev.device());
+  switch (kind) {
+    case GATHER: gpu ? ops_gather_gpu(sb, b, bp, st) : ops_gather_cpu(sb, b, bp); break;
+    case SCATTER: gpu ? ops_scatter_gpu(sb, b, bp, set, st) : ops_scatter_cpu(sb, b, bp, set); break;
+    case RMW: ops_scatter_rmw_gpu(sb, b, bp, st); break;
+    case EXTRACT: gpu ? ops_extract_gpu(sb, b, a, bp, st) : ops_extract_cpu(sb, b, a, bp); break;
+    case REFRESH: gpu ? ops_refresh_gpu(sb, b, a, bp, st) : ops_refresh_cpu(sb, b, a, bp); break;
+    case ZERO: gpu ? ops_zero_gpu(sb, b, st) : ops_zero_cpu(sb, b); break;
+    case SQNORM: gpu ? ops_delta_sqnorm_gpu(sb, b, a, bp, st) : ops_delta_sqnorm_cpu(sb, b, a, bp); break;
+  }
+}
+
+void slab_keys_op(const std::string& op, torch::Tensor dev, torch::Tensor keys, int64_t len,
+                  int64_t plen, int64_t world, int64_t rank, torch::Tensor buf, bool set) {
+  const bool gather = op == "gather_keys";
+  TORCH_CHECK(gather || op == "scatter_keys", "slab_keys_op: unknown op '", op, "'");
+  TORCH_CHECK(!(gather && set), "slab_keys_op: set applies to scatter_keys only");
+  const bool gpu = dev.is_cuda();
+  TORCH_CHECK(!gpu || hip_available(), "slab_keys_op: CUDA tensor but no HIP device");
+  check_slab_tensor(dev, torch::kFloat32, "dev slab");
+  check_slab_tensor(buf, torch::kFloat32, "buf");
+  TORCH_CHECK(buf.device() == dev.device(), "slab_keys_op: buf and dev on different devices");
+  const int64_t n = keys.numel();
+  check_host_batch_tensor(keys, torch::kInt64, n, "keys");
+  TORCH_CHECK(n <= std::numeric_limits<int>::max(), "slab_keys_op: batch too large");
+  TORCH_CHECK(len >= 1 && plen >= len && plen <= std::numeric_limits<int32_t>::max(),
+              "slab_keys_op: need 1 <= len <= plen");
+  // the kernels take the float4 path on len % 4 == 0 alone
+  TORCH_CHECK((len & 3) != 0 || (plen & 3) == 0, "slab_keys_op: len % 4 == 0 needs plen % 4 == 0");
+  TORCH_CHECK(world >= 1 && rank >= 0 && rank < world, "slab_keys_op: bad world / rank");
+  TORCH_CHECK(n * len <= buf.numel(), "slab_keys_op: buf holds fewer than n rows");
+  const int64_t* kp = keys.data_ptr<int64_t>();
+  const int64_t rows = dev.numel() / plen;  // whole slots only
+  for (int64_t i = 0; i < n; ++i) {
+    TORCH_CHECK(kp[i] >= 0, "slab_keys_op: keys[", i, "] is negative");
+    TORCH_CHECK(kp[i] % world != rank || kp[i] / world < rows, "slab_keys_op: keys[", i, "] = ",
+                kp[i], " lies past the slab's ", rows, " slots");
+  }
+  torch::Tensor k_d = gpu ? keys.to(dev.device()) : keys;
+  SlabBases sb{dev.data_ptr<float>(), nullptr};
+  KeyBatch b{k_d.data_ptr<int64_t>(), (int)n, (int32_t)len, (int32_t)plen, (int)world, (int)rank};
+  void* st = current_stream(dev.device());
+  if (gather)
+    gpu ? ops_gather_keys_gpu(sb, b, fp(buf), st) : ops_gather_keys_cpu(sb, b, fp(buf));
+  else
+    gpu ? ops_scatter_keys_gpu(sb, b, cfp(buf), set, st) : ops_scatter_keys_cpu(sb, b, cfp(buf), set);
+}
+
 }  // namespace adapm
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -3936,6 +4092,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("w2v_sgns_step", &w2v_sgns_step, py::call_guard<py::gil_scoped_release>());
   m.def("mf_update_step", &mf_update_step, py::call_guard<py::gil_scoped_release>());
   m.def("mf_loss", &mf_loss, py::call_guard<py::gil_scoped_release>());
+  // test-only entries into the slab ops (docs/ARCHITECTURE.md)
+  m.def("slab_op", &slab_op, py::arg("op"), py::arg("dev"), py::arg("host"), py::arg("src_off"),
+        py::arg("dst_off"), py::arg("lens"), py::arg("aux_off"), py::arg("buf"), py::arg("set"),
+        py::call_guard<py::gil_scoped_release>());
+  m.def("slab_keys_op", &slab_keys_op, py::arg("op"), py::arg("dev"), py::arg("keys"),
+        py::arg("len"), py::arg("plen"), py::arg("world"), py::arg("rank"), py::arg("buf"),
+        py::arg("set"), py::call_guard<py::gil_scoped_release>());
   py::class_<UniformStream>(m, "UniformStream")
       .def(py::init<int64_t, int64_t, std::string>(), py::arg("lo"), py::arg("hi"),
            py::arg("device"))

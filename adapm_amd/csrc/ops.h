@@ -49,7 +49,8 @@ void ops_scatter_rmw_gpu(const SlabBases& slab, const OpsBatch& b, const float* 
 // out[dst_off[i]] = ||slab[src_off[i]..] - slab[sync_off[i]..]||^2.
 // Drives the reference's --sys.sync.threshold ("send only deltas whose
 // norm clears the threshold"; sync_manager.h:601-662) without reading
-// the values back to the host.
+// the values back to the host. A skipped entry (src_off -1) leaves its
+// out element unwritten.
 void ops_delta_sqnorm_gpu(const SlabBases& slab, const OpsBatch& b, const int64_t* sync_off,
                           float* out, void* stream);
 void ops_delta_sqnorm_cpu(const SlabBases& slab, const OpsBatch& b, const int64_t* sync_off,
@@ -88,14 +89,6 @@ void ops_gather_keys_gpu(const SlabBases& slab, const KeyBatch& b, float* out, v
 void ops_gather_keys_cpu(const SlabBases& slab, const KeyBatch& b, float* out);
 void ops_scatter_keys_gpu(const SlabBases& slab, const KeyBatch& b, const float* in, bool set, void* stream);
 void ops_scatter_keys_cpu(const SlabBases& slab, const KeyBatch& b, const float* in, bool set);
-
-// Sorted scatter-add (identity layout): keys pre-sorted on device with the
-// permutation into `in` rows. Consecutive duplicate keys are pre-summed in
-// registers, so hot keys (Zipf pushes) cost one atomic per 16-row chunk
-// instead of one per row — removes atomic contention.
-void ops_scatter_sorted_gpu(const SlabBases& slab, const int64_t* sorted_keys,
-                            const int64_t* perm, int n, int32_t len, int32_t plen, int world,
-                            int rank, const float* in, void* stream);
 
 bool hip_available();
 

@@ -111,6 +111,7 @@ void ops_delta_sqnorm_cpu(const SlabBases& slab, const OpsBatch& b, const int64_
                           float* out) {
   for (int i = 0; i < b.n; ++i) {
     int64_t v = b.src_off[i], sy = sync_off[i];
+    if (v < 0) continue;
     const float* vb = sel_base_c(slab, v);
     const float* sb = sel_base_c(slab, sy);
     float acc = 0.f;

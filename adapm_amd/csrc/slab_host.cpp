@@ -41,6 +41,18 @@ int adapm_host_arena_alloc(long long floats, int want_device_visible, void** hos
   return 0;
 }
 
+// device-visible alias of pinned host memory somebody else allocated (a
+// pinned torch tensor); fails for memory the device cannot read
+int adapm_host_device_ptr(void* host_ptr, void** dev_ptr) {
+  void* d = nullptr;
+  if (hipHostGetDevicePointer(&d, host_ptr, 0) != hipSuccess || !d) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  *dev_ptr = d;
+  return 0;
+}
+
 void adapm_host_arena_free(void* host_ptr, int was_device_visible) {
   if (!host_ptr) return;
   if (was_device_visible)

@@ -294,7 +294,7 @@ struct ChannelState {
 // The state tensor is read and written by the draws in stream order, so
 // all work on it stays on one stream at a time: a call that arrives on
 // another stream first waits for the previous owner stream to drain (as
-// Server::fused_plain_ok does for the row marks) and then owns it.
+// Server::fused_plain_ok does for the row tags) and then owns it.
 class UniformStream {
  public:
   UniformStream(int64_t lo, int64_t hi, const std::string& device)
@@ -2787,31 +2787,35 @@ class Server {
   //   (a) the server was set up for a single worker thread (a second
   //       worker could push on its own stream at any time), and
   //   (b) every fused step so far came in on one stream, the one that
-  //       owns the row marks. The first call on another stream waits for
+  //       owns the row tags. The first call on another stream waits for
   //       the owner stream to drain and turns the plain path off for good.
   // Every other call runs the all-atomic kernel, which tolerates
   // concurrent writers. (One worker thread that pushes on a second stream
   // without synchronizing it with the first has no order between its own
   // ops, with or without this.) Called with fused_mu_ held; allocates the
-  // marks (2 bits per key, zeroed once) on first use.
+  // row tags (kernels.h) on first use: one 4-byte word per key, 40 MB at
+  // the benchmark's 10,001,000 keys beside a 41 GB slab, and their bitmap
+  // behind them in the same tensor, one bit per key. They are not zeroed,
+  // and nothing cleans them after a step: every step's passes write each
+  // word that step goes on to read.
   bool fused_plain_ok(void* st) {
     if (clocks_.size() != 1 || fused_multi_stream_) return false;
-    if (!fused_marks_.defined()) {
+    if (!fused_tags_.defined()) {
       if (getenv("ADAPM_FUSED_ATOMIC")) {  // A/B switch: keep the all-atomic kernel
         fused_multi_stream_ = true;
         return false;
       }
-      fused_marks_ = torch::zeros({rowmark_words(num_keys_)},
-                                  torch::TensorOptions().dtype(torch::kInt32).device(dev_));
+      fused_tags_ = torch::empty({33 * rowtag_words(num_keys_)},
+                                 torch::TensorOptions().dtype(torch::kInt32).device(dev_));
       if (getenv("ADAPM_FUSED_STATS"))
         fused_shared_stat_ =
             torch::zeros({1}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
-      fused_marks_stream_ = st;
+      fused_tags_stream_ = st;
       return true;
     }
-    if (st == fused_marks_stream_) return true;
+    if (st == fused_tags_stream_) return true;
 #ifdef ADAPM_WITH_HIP
-    hipStreamSynchronize((hipStream_t)fused_marks_stream_);
+    hipStreamSynchronize((hipStream_t)fused_tags_stream_);
 #endif
     fused_multi_stream_ = true;
     return false;
@@ -2844,14 +2848,27 @@ class Server {
   // to the allocator with an event on the stream, so it is not reused
   // before that kernel has run. The range check rides the copy loop; a bad
   // key throws before anything is enqueued.
+  // The two halves are separate because the fused ComplEx step lets its tag
+  // pass do the upload (upload_keys with `tags`): host_keys stages and
+  // checks, upload_keys enqueues the one launch that reads the blob.
+  struct HostKeys {
+    torch::Tensor blob;      // pinned, all parts back to back
+    std::vector<int64_t> n;  // length of each part
+  };
   struct StagedKeys {
     torch::Tensor dev;  // keeps the device blob alive
     std::vector<const int64_t*> ptr;
   };
   StagedKeys stage_keys(const char* name, std::initializer_list<const torch::Tensor*> parts) {
+    return upload_keys(name, host_keys(parts));
+  }
+
+  HostKeys host_keys(std::initializer_list<const torch::Tensor*> parts) {
+    HostKeys hk;
     int64_t total = 0;
     for (auto* t : parts) {
       check_keys(*t);
+      hk.n.push_back(t->numel());
       total += t->numel();
     }
     auto blob = torch::empty(
@@ -2871,22 +2888,37 @@ class Server {
     }
     if (bad)
       for (auto* t : parts) check_key_range(*t);  // names the offending key
+    hk.blob = blob;
+    return hk;
+  }
+
+  // With `tags` the upload is the tag pass of a fused ComplEx step
+  // (keys_land_gpu): the staged keys are occurrences 0..total of the step,
+  // the n_dev keys at dev_keys (already on the device) the ones after them.
+  StagedKeys upload_keys(const char* name, const HostKeys& hk, uint32_t* tags = nullptr,
+                         const int64_t* dev_keys = nullptr, int64_t n_dev = 0) {
+    const torch::Tensor& blob = hk.blob;
+    const int64_t total = blob.numel();
     StagedKeys sk;
     sk.dev = torch::empty({total}, torch::TensorOptions().dtype(torch::kInt64).device(dev_));
 #ifdef ADAPM_WITH_HIP
     auto stream = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(dev_.index());
-    TORCH_CHECK(copy_keys_gpu(sk.dev.data_ptr<int64_t>(), blob.data_ptr<int64_t>(), total,
-                              (void*)stream.stream()),
-                name, ": the pinned key staging buffer is not visible to the device");
+    const bool ok =
+        tags ? keys_land_gpu(tags, sk.dev.data_ptr<int64_t>(), blob.data_ptr<int64_t>(), total,
+                             dev_keys, n_dev, (void*)stream.stream())
+             : copy_keys_gpu(sk.dev.data_ptr<int64_t>(), blob.data_ptr<int64_t>(), total,
+                             (void*)stream.stream());
+    TORCH_CHECK(ok, name, ": the pinned key staging buffer is not visible to the device");
+    // after the launch that reads the blob, whichever it was
     at::getHostAllocator(at::kCUDA)->record_event(
         blob.data_ptr(), blob.storage().data_ptr().get_context(), stream.unwrap());
 #else
     TORCH_CHECK(false, name, ": built without HIP");
 #endif
     const int64_t* dp = sk.dev.data_ptr<int64_t>();
-    for (auto* t : parts) {
+    for (int64_t n : hk.n) {
       sk.ptr.push_back(dp);
-      dp += t->numel();
+      dp += n;
     }
     return sk;
   }
@@ -2902,9 +2934,13 @@ class Server {
     check_step_lanes("kge_step_fused", "D/2", D / 2);
     int64_t B = keys_s.numel();
     TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B);
+    // the tag pass numbers the occurrences in 32 bits, ROWTAG_SHARED aside
+    TORCH_CHECK(N >= 0 && (3 + N) * B < (int64_t)ROWTAG_SHARED,
+                "kge_step_fused: too many keys in one step");
+    HostKeys hk;
     StagedKeys sk;
     torch::Tensor drawn;
-    const int64_t* kn;
+    const int64_t* kn = nullptr;
     if (us) {
       // device keys never reach the kernel unvalidated: the stream can only
       // produce keys of [lo, hi), and that range is checked here
@@ -2913,15 +2949,16 @@ class Server {
       TORCH_CHECK(us->device() == dev_,
                   "kge_step_fused_sampled: stream is not on the store's device");
       TORCH_CHECK(N >= 0 && B * N > 0, "kge_step_fused_sampled: nothing to draw");
-      sk = stage_keys("kge_step_fused", {&keys_s, &keys_r, &keys_o});
+      // staged and checked now, uploaded below, behind the draw: the draw
+      // does not depend on s, r and o
+      hk = host_keys({&keys_s, &keys_r, &keys_o});
       drawn = us->draw(B * N);
       kn = drawn.data_ptr<int64_t>();
     } else {
       TORCH_CHECK(keys_neg->numel() == B * N);
-      sk = stage_keys("kge_step_fused", {&keys_s, &keys_r, &keys_o, keys_neg});
-      kn = sk.ptr[3];
+      hk = host_keys({&keys_s, &keys_r, &keys_o, keys_neg});
     }
-    const int64_t *ks = sk.ptr[0], *kr = sk.ptr[1], *ko = sk.ptr[2];
+    const int64_t n_dev = us ? B * N : 0;  // occurrences that are on the device already
 
     auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
     void* st = current_stream(dev_);
@@ -2934,25 +2971,31 @@ class Server {
       // while the step runs, and a plain read-modify-write would lose them.
       std::unique_lock<std::mutex> mg(fused_mu_);
       if (fused_plain_ok(st)) {
-        // pre-pass, step and clean-up are enqueued under the lock: the row
-        // marks are per server, and a second caller must find them zeroed
-        RowMarkKeys mk{{ks, kr, ko, kn}, {B, B, B, B * N}, 4};
-        auto* marks = reinterpret_cast<uint32_t*>(fused_marks_.data_ptr<int32_t>());
-        rowmark_set_gpu(marks, mk, st);
+        // tag pass (which is also the key upload), flag pass, bits pass and
+        // step are enqueued under the lock: the row tags are per server, and
+        // a second caller's passes must not land between this one's
+        auto* tags = reinterpret_cast<uint32_t*>(fused_tags_.data_ptr<int32_t>());
+        uint32_t* bits = tags + 32 * rowtag_words(num_keys_);
+        sk = upload_keys("kge_step_fused", hk, tags, kn, n_dev);
+        if (!us) kn = sk.ptr[3];
+        // s | r | o (| host negatives) are one array on the device
+        RowTagKeys tk{{sk.ptr[0], kn, nullptr, nullptr}, {hk.blob.numel(), n_dev, 0, 0}, 2};
+        rowtag_flag_gpu(tags, tk, st);
+        rowtag_bits_gpu(tags, bits, tk, st);
         kge_complex_step_fused_gpu(
-            slab_.data, mk.keys[0], mk.keys[1], mk.keys[2], mk.keys[3], loss.data_ptr<float>(),
-            (int)B, (int)N, (int)D, Slab::padded(uniform_len_), world_, (float)lr, (float)eps,
-            st, marks,
+            slab_.data, sk.ptr[0], sk.ptr[1], sk.ptr[2], kn, loss.data_ptr<float>(), (int)B,
+            (int)N, (int)D, Slab::padded(uniform_len_), world_, (float)lr, (float)eps, st, bits,
             fused_shared_stat_.defined()
                 ? reinterpret_cast<unsigned long long*>(fused_shared_stat_.data_ptr<int64_t>())
                 : nullptr);
-        rowmark_clear_gpu(marks, mk, st);
         stat_fused_plain_ += 1;
       } else {
         mg.unlock();
-        kge_complex_step_fused_gpu(slab_.data, ks, kr, ko, kn, loss.data_ptr<float>(), (int)B,
-                                   (int)N, (int)D, Slab::padded(uniform_len_), world_, (float)lr,
-                                   (float)eps, st);
+        sk = upload_keys("kge_step_fused", hk);
+        if (!us) kn = sk.ptr[3];
+        kge_complex_step_fused_gpu(slab_.data, sk.ptr[0], sk.ptr[1], sk.ptr[2], kn,
+                                   loss.data_ptr<float>(), (int)B, (int)N, (int)D,
+                                   Slab::padded(uniform_len_), world_, (float)lr, (float)eps, st);
         stat_fused_atomic_ += 1;
       }
     }
@@ -3722,11 +3765,11 @@ class Server {
       stat_dropped_records_{0}, stat_delta_overhops_{0}, stat_bytes_sent_{0},
       stat_bytes_recv_{0}, stat_sampling_checks_{0};
 
-  // world==1 fused step: per-batch row marks (see fused_plain_ok)
+  // world==1 fused step: per-batch row tags (see fused_plain_ok)
   std::mutex fused_mu_;
-  torch::Tensor fused_marks_;        // int32 words, 2 bits per key, all-zero between steps
+  torch::Tensor fused_tags_;         // int32[num_keys], 4 bytes per key, never cleaned
   torch::Tensor fused_shared_stat_;  // int64[1], only with ADAPM_FUSED_STATS
-  void* fused_marks_stream_ = nullptr;
+  void* fused_tags_stream_ = nullptr;
   bool fused_multi_stream_ = false;
   std::atomic<int64_t> stat_fused_plain_{0}, stat_fused_atomic_{0};
 };
@@ -4079,6 +4122,46 @@ void slab_keys_op(const std::string& op, torch::Tensor dev, torch::Tensor keys, 
     gpu ? ops_scatter_keys_gpu(sb, b, cfp(buf), set, st) : ops_scatter_keys_cpu(sb, b, cfp(buf), set);
 }
 
+// ---- test-only entry into the row tags (tests/test_rowtags.py) ----
+// Up to four CPU key arrays, counted as one list of occurrences: allocates
+// tags and bitmap for num_keys rows on the current GPU (uninitialised, as
+// the server's are), runs the tag, flag and bits passes the fused ComplEx
+// step runs, and returns, per occurrence, whether the bitmap calls its row
+// shared.
+torch::Tensor rowtag_shared_mask(std::vector<torch::Tensor> keys, int64_t num_keys) {
+  TORCH_CHECK(hip_available(), "rowtag_shared_mask: no HIP device");
+  TORCH_CHECK(!keys.empty() && keys.size() <= 4, "rowtag_shared_mask: one to four key arrays");
+  TORCH_CHECK(num_keys >= 1 && num_keys <= std::numeric_limits<int32_t>::max(),
+              "rowtag_shared_mask: bad num_keys");
+  const torch::Device dev(torch::kCUDA, c10::hip::current_device());
+  std::vector<torch::Tensor> dk;
+  RowTagKeys tk{{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}, (int)keys.size()};
+  int64_t total = 0;
+  for (size_t a = 0; a < keys.size(); ++a) {
+    const int64_t n = keys[a].numel();
+    check_host_batch_tensor(keys[a], torch::kInt64, n, "keys");
+    const int64_t* kp = keys[a].data_ptr<int64_t>();
+    for (int64_t i = 0; i < n; ++i)
+      TORCH_CHECK(kp[i] >= 0 && kp[i] < num_keys, "rowtag_shared_mask: key out of range: ", kp[i]);
+    dk.push_back(keys[a].to(dev));
+    tk.keys[a] = dk.back().data_ptr<int64_t>();
+    tk.n[a] = n;
+    total += n;
+  }
+  TORCH_CHECK(total < (int64_t)ROWTAG_SHARED, "rowtag_shared_mask: too many occurrences");
+  const int64_t words = rowtag_words(num_keys);
+  auto tags = torch::empty({33 * words}, torch::TensorOptions().dtype(torch::kInt32).device(dev));
+  auto* tp = reinterpret_cast<uint32_t*>(tags.data_ptr<int32_t>());
+  void* st = current_stream(dev);
+  rowtag_tag_gpu(tp, tk, st);
+  rowtag_flag_gpu(tp, tk, st);
+  rowtag_bits_gpu(tp, tp + 32 * words, tk, st);
+  // the step's own question, asked of the bitmap: bit (key & 31) of word key >> 5
+  auto all = torch::cat(dk);
+  auto word = tags.narrow(0, 32 * words, words).index_select(0, all.div(32, "floor"));
+  return word.bitwise_right_shift(all.remainder(32).to(torch::kInt32)).bitwise_and(1).eq(1);
+}
+
 }  // namespace adapm
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -4099,6 +4182,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("slab_keys_op", &slab_keys_op, py::arg("op"), py::arg("dev"), py::arg("keys"),
         py::arg("len"), py::arg("plen"), py::arg("world"), py::arg("rank"), py::arg("buf"),
         py::arg("set"), py::call_guard<py::gil_scoped_release>());
+  // test-only entry into the row tags of the fused ComplEx step
+  m.def("rowtag_shared_mask", &rowtag_shared_mask, py::arg("keys"), py::arg("num_keys"),
+        py::call_guard<py::gil_scoped_release>());
   py::class_<UniformStream>(m, "UniformStream")
       .def(py::init<int64_t, int64_t, std::string>(), py::arg("lo"), py::arg("hi"),
            py::arg("device"))

@@ -33,37 +33,68 @@ void kge_complex_step_cpu(const float* s, const float* r, const float* o, const 
                           float* ds, float* dr, float* do_, float* dneg, float* loss,
                           int B, int N, int D, float lr, float eps);
 
-// Row marks for the fused slab-direct steps: which key occurrences of one
+// Row tags for the fused slab-direct steps: which key occurrences of one
 // batch share their slab row with another occurrence of the same batch.
-// `marks` is a zeroed device bitmap of rowmark_words(rows) words, two bits
-// per row. rowmark_set_gpu marks every occurrence of up to four key arrays
-// (counted together, whatever their role); the step kernel then reads
-// "shared or unique" per occurrence; rowmark_clear_gpu, given the same
-// keys, restores the bitmap to all-zero at the cost of the batch, not of
-// the table. All three go on one stream, in that order. Keys must be row
-// indices (single-rank identity layout: row == key).
-struct RowMarkKeys {
+// `tags` is a device array of one word per row; its contents before a step
+// do not matter. Occurrence i is position i in the concatenation of up to
+// four key arrays (counted together, whatever their role), and the total
+// must stay below ROWTAG_SHARED. Three launches on one stream, then the step:
+//   tag   every occurrence i stores tags[row] = i; where several name one
+//         row, any one of them wins;
+//   flag  every occurrence i loads tags[row] and stores ROWTAG_SHARED there
+//         unless it finds its own i;
+//   bits  every occurrence rewrites the whole word of its row in `bits`, one
+//         bit per row, from the 32 tags that word stands for.
+// After tag and flag, tags[row] == ROWTAG_SHARED exactly for the rows that
+// two or more occurrences name: a row named once keeps its i; of a row named
+// more than once all occurrences but the winner read the winner's index or
+// ROWTAG_SHARED, never their own, and store ROWTAG_SHARED. The step reads
+// bit `row` of `bits`, a bitmap small enough to stay in cache (the tags are
+// not: a step kernel that read them gave back all that the passes saved,
+// profiles/kge_rowtags_stats.txt). The
+// tag pass writes every tag, and the bits pass every bitmap word, that the
+// step goes on to ask about, so nothing is cleaned up afterwards and no
+// launch holds a read-modify-write: racing stores to one word all lead to
+// the same final state, and the kernel boundaries order the passes and the
+// step. Tags and bits of rows outside the batch are stale and never read.
+// Keys must be row indices (single-rank identity layout: row == key) below
+// `rows`; `tags` holds 32 * rowtag_words(rows) words, 128-byte aligned, and
+// `bits` rowtag_words(rows).
+constexpr uint32_t ROWTAG_SHARED = 0xFFFFFFFFu;
+struct RowTagKeys {
   const int64_t* keys[4];  // DEVICE pointers
   int64_t n[4];
   int count;  // arrays in use
 };
-inline int64_t rowmark_words(int64_t rows) { return (rows + 15) / 16; }
-void rowmark_set_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream);
-void rowmark_clear_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream);
+inline int64_t rowtag_words(int64_t rows) { return (rows + 31) / 32; }
+void rowtag_tag_gpu(uint32_t* tags, const RowTagKeys& ks, void* stream);  // tests only
+void rowtag_flag_gpu(uint32_t* tags, const RowTagKeys& ks, void* stream);
+void rowtag_bits_gpu(const uint32_t* tags, uint32_t* bits, const RowTagKeys& ks, void* stream);
+
+// The tag pass of a step whose first n_copy keys still sit in pinned,
+// device-visible host memory: occurrence i < n_copy reads src_host[i],
+// writes it to dst[i] (device) and tags its row; occurrence n_copy + j,
+// j < n_dev, tags the row of dev_keys[j] (device keys, e.g. drawn
+// negatives). One launch on `stream` in place of copy_keys_gpu plus a tag
+// pass. Returns false, with nothing enqueued, if src_host is not
+// device-visible.
+bool keys_land_gpu(uint32_t* tags, int64_t* dst, const int64_t* src_host, int64_t n_copy,
+                   const int64_t* dev_keys, int64_t n_dev, void* stream);
 
 // FUSED ComplEx step: reads entity/relation rows DIRECTLY from the slab
 // and accumulates the AdaGrad-transformed deltas back — no intermediate
 // pull/push buffers (the classic path pays a gather write + kernel read +
 // delta write + scatter read; this saves all four). keys_* are DEVICE
 // int64 pointers.
-// Writes: with `marks` (filled by rowmark_set_gpu for exactly these keys,
-// world == 1 only) plain stores on rows unique in the batch, atomic adds on
-// shared ones — a float atomic costs ~4-5x the plain store of the same
-// bytes and only a shared row needs it. The caller guarantees that nothing
-// else writes the slab while the launch runs. Without marks every write is
-// atomic. Either way duplicate keys within the batch see hogwild-style
-// concurrent updates (async-PS semantics). shared_stat (optional, with
-// marks) accumulates the number of occurrences that took the atomic path.
+// Writes: with `bits` (the row tags' bitmap after the three passes over
+// exactly these keys, world == 1 only) plain stores on rows unique in the
+// batch, atomic adds on shared ones — a float atomic costs ~4-5x the plain
+// store of the same bytes and only a shared row needs it. The caller
+// guarantees that nothing else writes the slab while the launch runs.
+// Without bits every write is atomic. Either way duplicate keys within the
+// batch see hogwild-style concurrent updates (async-PS semantics).
+// shared_stat (optional, with bits) accumulates the number of occurrences
+// that took the atomic path.
 // Addressing modes (row_at): world >= 1 — identity layout, key k at
 // (k/world)*plen (single-rank fast path, zero host work); world == 0 —
 // keys_* carry precomputed float OFFSETS into the slab (the world>1 /
@@ -72,7 +103,7 @@ void rowmark_clear_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream);
 void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
                                 const int64_t* keys_o, const int64_t* keys_neg, float* loss,
                                 int B, int N, int D, int32_t plen, int world, float lr,
-                                float eps, void* stream, const uint32_t* marks = nullptr,
+                                float eps, void* stream, const uint32_t* bits = nullptr,
                                 unsigned long long* shared_stat = nullptr);
 
 // CPU tier of the offsets-mode fused steps (exercises the world>1 fused
@@ -89,9 +120,9 @@ void mf_update_step_fused_offs_cpu(float* slab, const int64_t* offs_w, const int
 
 // FUSED SGNS step: slab-direct reads + AdaGrad writes, same addressing
 // modes as kge_complex_step_fused_gpu. Every write is atomic: the kernel
-// takes no row marks. It writes through the same per-lane helper as the
+// takes no row tags. It writes through the same per-lane helper as the
 // ComplEx step (slab_adagrad in kernels_hip.hip) with shared = true, so
-// adopting the marks means passing a row's mark there instead.
+// adopting the tags means passing the row's bit there instead.
 void w2v_sgns_step_fused_gpu(float* slab, const int64_t* keys_ctr, const int64_t* keys_ctx,
                              const int64_t* keys_neg, float* loss, int B, int N, int D,
                              int32_t plen, int world, float lr, float eps, void* stream);

@@ -597,13 +597,10 @@ __device__ inline float* row_at(float* slab, int64_t v, int32_t plen, int world)
   return world ? slab + (v / world) * (int64_t)plen : slab + v;
 }
 
-// ---- per-launch row marks (see kernels.h): two bits per slab row, 16
-// rows per word. Bit 0 = "an occurrence of this batch names the row",
-// bit 1 = "a second one does too".
-__device__ inline uint32_t* rowmark_word(uint32_t* marks, int64_t row) { return marks + (row >> 4); }
-__device__ inline int rowmark_shift(int64_t row) { return 2 * (int)(row & 15); }
-
-__device__ inline int64_t rowmark_key(const RowMarkKeys& ks, int64_t i) {
+// ---- per-launch row tags (see kernels.h): one word per slab row. Every
+// store below is a plain store of a whole word; none of the passes holds a
+// read-modify-write.
+__device__ inline int64_t rowtag_key(const RowTagKeys& ks, int64_t i) {
   // occurrence i of the concatenated key arrays
   int a = 0;
   while (a < ks.count - 1 && i >= ks.n[a]) {
@@ -613,46 +610,119 @@ __device__ inline int64_t rowmark_key(const RowMarkKeys& ks, int64_t i) {
   return ks.keys[a][i];
 }
 
-__global__ void k_rowmark_set(uint32_t* __restrict__ marks, RowMarkKeys ks, int64_t total) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  int64_t row = rowmark_key(ks, i);
-  uint32_t bit = 1u << rowmark_shift(row);
-  uint32_t old = atomicOr(rowmark_word(marks, row), bit);
-  if ((old & bit) && !(old & (bit << 1))) atomicOr(rowmark_word(marks, row), bit << 1);
+// tag pass, occurrence i: whoever stores last owns the row
+__device__ inline void rowtag_tag(uint32_t* tags, int64_t row, int64_t i) {
+  tags[row] = (uint32_t)i;
 }
 
-// Every word that k_rowmark_set touched held only marks of this batch, so
-// storing 0 over it (possibly from several threads) restores all-zero.
-__global__ void k_rowmark_clear(uint32_t* __restrict__ marks, RowMarkKeys ks, int64_t total) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  *rowmark_word(marks, rowmark_key(ks, i)) = 0u;
+// flag pass, occurrence i: a tag that is not mine means the row has a
+// second occurrence (its owner's index, or ROWTAG_SHARED already)
+__device__ inline void rowtag_flag(uint32_t* tags, int64_t row, int64_t i) {
+  if (tags[row] != (uint32_t)i) tags[row] = ROWTAG_SHARED;
 }
 
-void rowmark_set_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream) {
+// Tag pass fused with the key upload: see keys_land_gpu in kernels.h.
+__global__ void k_keys_land(uint32_t* __restrict__ tags, int64_t* __restrict__ dst,
+                            const int64_t* __restrict__ src, int64_t n_copy,
+                            const int64_t* __restrict__ dev_keys, int64_t total) {
+  int64_t i = (int64_t)blockIdx.x * KT + threadIdx.x;
+  if (i >= total) return;
+  int64_t row;
+  if (i < n_copy) {
+    row = src[i];
+    dst[i] = row;
+  } else {
+    row = dev_keys[i - n_copy];
+  }
+  rowtag_tag(tags, row, i);
+}
+
+// the tag pass alone, over keys that are already on the device
+__global__ void k_rowtag_tag(uint32_t* __restrict__ tags, RowTagKeys ks, int64_t total) {
+  int64_t i = (int64_t)blockIdx.x * KT + threadIdx.x;
+  if (i >= total) return;
+  rowtag_tag(tags, rowtag_key(ks, i), i);
+}
+
+__global__ void k_rowtag_flag(uint32_t* __restrict__ tags, RowTagKeys ks, int64_t total) {
+  int64_t i = (int64_t)blockIdx.x * KT + threadIdx.x;
+  if (i >= total) return;
+  rowtag_flag(tags, rowtag_key(ks, i), i);
+}
+
+// bits pass, occurrence i: rewrite the whole bitmap word of its row from the
+// 32 tags behind it (one aligned 128-byte line). Every writer of a word
+// stores the same value, because the tags no longer change. Tags of rows
+// that are not in the batch are stale; so are their bits, which nobody reads.
+__global__ void k_rowtag_bits(const uint32_t* __restrict__ tags, uint32_t* __restrict__ bits,
+                              RowTagKeys ks, int64_t total) {
+  int64_t i = (int64_t)blockIdx.x * KT + threadIdx.x;
+  if (i >= total) return;
+  const int64_t w = rowtag_key(ks, i) >> 5;
+  const uint4* t = reinterpret_cast<const uint4*>(tags + (w << 5));
+  uint32_t word = 0;
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const uint4 v = t[q];
+    word |= ((uint32_t)(v.x == ROWTAG_SHARED) | (uint32_t)(v.y == ROWTAG_SHARED) << 1 |
+             (uint32_t)(v.z == ROWTAG_SHARED) << 2 | (uint32_t)(v.w == ROWTAG_SHARED) << 3)
+            << (4 * q);
+  }
+  bits[w] = word;
+}
+
+static int64_t rowtag_total(const RowTagKeys& ks) {
   int64_t total = 0;
   for (int a = 0; a < ks.count; ++a) total += ks.n[a];
-  if (total == 0) return;
-  hipLaunchKernelGGL(k_rowmark_set, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
-                     (hipStream_t)stream, marks, ks, total);
+  return total;
 }
 
-void rowmark_clear_gpu(uint32_t* marks, const RowMarkKeys& ks, void* stream) {
-  int64_t total = 0;
-  for (int a = 0; a < ks.count; ++a) total += ks.n[a];
+void rowtag_tag_gpu(uint32_t* tags, const RowTagKeys& ks, void* stream) {
+  const int64_t total = rowtag_total(ks);
   if (total == 0) return;
-  hipLaunchKernelGGL(k_rowmark_clear, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
-                     (hipStream_t)stream, marks, ks, total);
+  hipLaunchKernelGGL(k_rowtag_tag, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
+                     (hipStream_t)stream, tags, ks, total);
+}
+
+void rowtag_flag_gpu(uint32_t* tags, const RowTagKeys& ks, void* stream) {
+  const int64_t total = rowtag_total(ks);
+  if (total == 0) return;
+  hipLaunchKernelGGL(k_rowtag_flag, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
+                     (hipStream_t)stream, tags, ks, total);
+}
+
+void rowtag_bits_gpu(const uint32_t* tags, uint32_t* bits, const RowTagKeys& ks, void* stream) {
+  const int64_t total = rowtag_total(ks);
+  if (total == 0) return;
+  hipLaunchKernelGGL(k_rowtag_bits, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
+                     (hipStream_t)stream, tags, bits, ks, total);
+}
+
+bool keys_land_gpu(uint32_t* tags, int64_t* dst, const int64_t* src_host, int64_t n_copy,
+                   const int64_t* dev_keys, int64_t n_dev, void* stream) {
+  const int64_t total = n_copy + n_dev;
+  if (total <= 0) return true;
+  void* src = nullptr;  // fails for memory the device cannot read
+  if (n_copy > 0 &&
+      (hipHostGetDevicePointer(&src, const_cast<int64_t*>(src_host), 0) != hipSuccess || !src)) {
+    (void)hipGetLastError();
+    return false;
+  }
+  hipLaunchKernelGGL(k_keys_land, dim3((unsigned)((total + KT - 1) / KT)), dim3(KT), 0,
+                     (hipStream_t)stream, tags, dst, static_cast<const int64_t*>(src), n_copy,
+                     dev_keys, total);
+  return true;
 }
 
 // UNIQ: is the row shared with another occurrence of this batch? The word
 // address depends only on the key, so this load runs beside the row loads
-// and is uniform across the block.
+// and is uniform across the block. It reads the bitmap and not the tags:
+// the load is a scalar one whose latency the block waits out, and the
+// bitmap (1.25 MB at 10M keys) stays in cache where the tags (40 MB) do not.
 template <bool UNIQ>
-__device__ inline bool row_shared(const uint32_t* __restrict__ marks, int64_t key) {
+__device__ inline bool row_shared(const uint32_t* __restrict__ bits, int64_t key) {
   if (!UNIQ) return true;
-  return (marks[key >> 4] >> (rowmark_shift(key) + 1)) & 1u;
+  return (bits[key >> 5] >> (int)(key & 31)) & 1u;
 }
 
 // row = row + delta with a plain store, rounded exactly like the atomic it
@@ -666,7 +736,7 @@ __device__ inline float plain_add(float a, float delta) {
 // Fused kernels: one lane's AdaGrad update applied to the slab row itself,
 // *p_emb += delta and *p_acc += g^2. A row shared with another occurrence
 // of the batch takes atomics; the only writer of a row stores over the
-// values (emb, acc) it read. The SGNS and MF steps have no row marks and
+// values (emb, acc) it read. The SGNS and MF steps have no row tags and
 // pass shared = true.
 __device__ inline void slab_adagrad(float* p_emb, float* p_acc, float g, float emb, float acc,
                                     float lr, float eps, bool shared) {
@@ -709,27 +779,27 @@ __device__ inline void slab_adagrad(float* p_emb, float* p_acc, float g, float e
 
 // Fused ComplEx step — see kernels.h. Structure mirrors k_kge_step but
 // rows come from / return to the slab itself. UNIQ = false is the
-// all-atomic kernel (marks unused); UNIQ = true writes the rows that
-// `marks` shows to be unique in this batch with plain stores.
+// all-atomic kernel (bits unused); UNIQ = true writes the rows that the
+// row tags' `bits` show to be unique in this batch with plain stores.
 template <int KPT, bool UNIQ>
 __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __restrict__ keys_s,
                                  const int64_t* __restrict__ keys_r,
                                  const int64_t* __restrict__ keys_o,
                                  const int64_t* __restrict__ keys_neg, float* __restrict__ loss,
                                  int B, int N, int D, int32_t plen, int world, float lr,
-                                 float eps, const uint32_t* __restrict__ marks,
+                                 float eps, const uint32_t* __restrict__ bits,
                                  unsigned long long* __restrict__ shared_stat) {
   __shared__ float lds[KT / 64];
   const int dc = D >> 1;
-  // the marks imply the single-rank layout: a constant spares row_at the
+  // the bits imply the single-rank layout: a constant spares row_at the
   // 64-bit division
   const int w = UNIQ ? 1 : world;
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     const int64_t key_s = keys_s[b], key_r = keys_r[b];
     const float* sb = row_at(slab, key_s, plen, w);
     const float* rb = row_at(slab, key_r, plen, w);
-    const bool s_shared = row_shared<UNIQ>(marks, key_s);
-    const bool r_shared = row_shared<UNIQ>(marks, key_r);
+    const bool s_shared = row_shared<UNIQ>(bits, key_s);
+    const bool r_shared = row_shared<UNIQ>(bits, key_r);
     unsigned n_shared = (unsigned)s_shared + (unsigned)r_shared;
 
     float s_re[KPT], s_im[KPT], r_re[KPT], r_im[KPT];
@@ -755,7 +825,7 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
     for (int j = 0; j <= N; ++j) {
       int64_t ok = (j == 0) ? keys_o[b] : keys_neg[(int64_t)b * N + (j - 1)];
       float* ob = row_at(slab, ok, plen, w);
-      const bool o_shared = row_shared<UNIQ>(marks, ok);
+      const bool o_shared = row_shared<UNIQ>(bits, ok);
       n_shared += (unsigned)o_shared;
       float y = (j == 0) ? 1.f : -1.f;
       float part = 0.f;
@@ -811,18 +881,18 @@ __global__ void k_kge_step_fused(float* __restrict__ slab, const int64_t* __rest
 void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
                                 const int64_t* keys_o, const int64_t* keys_neg, float* loss,
                                 int B, int N, int D, int32_t plen, int world, float lr,
-                                float eps, void* stream, const uint32_t* marks,
+                                float eps, void* stream, const uint32_t* bits,
                                 unsigned long long* shared_stat) {
   if (B < 1) return;  // unlike the other steps, an empty batch enqueues nothing
-  // marks are indexed by key, which is the row only in the single-rank
+  // bits are indexed by key, which is the row only in the single-rank
   // identity layout; every other addressing mode stays all-atomic
-  const bool uniq = marks != nullptr && world == 1;
-  if (!uniq) marks = nullptr, shared_stat = nullptr;
+  const bool uniq = bits != nullptr && world == 1;
+  if (!uniq) bits = nullptr, shared_stat = nullptr;
   dispatch_kpt(D >> 1, [&](auto kpt) {
     constexpr int KPT = decltype(kpt)::value;
     hipLaunchKernelGGL((uniq ? k_kge_step_fused<KPT, true> : k_kge_step_fused<KPT, false>),
                        dim3(grid_for(B)), dim3(KT), 0, (hipStream_t)stream, slab, keys_s, keys_r,
-                       keys_o, keys_neg, loss, B, N, D, plen, world, lr, eps, marks,
+                       keys_o, keys_neg, loss, B, N, D, plen, world, lr, eps, bits,
                        shared_stat);
   });
 }

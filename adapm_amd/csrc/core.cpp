@@ -3843,6 +3843,78 @@ void kge_complex_score(torch::Tensor s, torch::Tensor r, torch::Tensor cand,
   }
 }
 
+// Row-strided fp32 matrix of the rank kernels: [rows][>= K], last dimension
+// contiguous; returns the row stride in floats.
+static int rank_rows(const torch::Tensor& t, int64_t K, const char* fn, const char* name) {
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32 && t.dim() == 2, fn, ": ", name,
+              " must be a 2-d float32 tensor");
+  TORCH_CHECK(t.size(0) < INT32_MAX, fn, ": ", name, " has too many rows");
+  if (t.numel() == 0) return (int)K;
+  TORCH_CHECK(K <= t.size(1), fn, ": K = ", K, " exceeds the row length ", t.size(1), " of ",
+              name);
+  TORCH_CHECK(t.size(1) == 1 || t.stride(1) == 1, fn, ": last dimension of ", name,
+              " must be contiguous");
+  if (t.size(0) == 1) return (int)K;  // the stride of a single row is never used
+  TORCH_CHECK(t.stride(0) >= K && t.stride(0) <= INT32_MAX, fn, ": row stride ", t.stride(0),
+              " of ", name, " must be in [K, 2^31)");
+  return (int)t.stride(0);
+}
+
+static void rank_vec(const torch::Tensor& t, torch::ScalarType dt, int64_t n,
+                     const torch::Device& dev, const char* fn, const char* name) {
+  TORCH_CHECK(t.scalar_type() == dt && t.is_contiguous() && t.numel() == n, fn, ": ", name,
+              " must be a contiguous ", dt, " tensor of ", n, " elements");
+  TORCH_CHECK(t.device() == dev, fn, ": ", name, " must be on ", dev);
+}
+
+// counts[b] += #{ e : dot_K(q[b], cand[e]) > base[b] or NaN } (kernels.h)
+void rank_count(torch::Tensor q, torch::Tensor cand, torch::Tensor base, torch::Tensor counts,
+                int64_t K, int64_t max_blocks) {
+  const char* fn = "rank_count";
+  TORCH_CHECK(K >= 1, fn, ": K must be >= 1");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= INT32_MAX, fn, ": max_blocks must be >= 0");
+  int qs = rank_rows(q, K, fn, "q"), cs = rank_rows(cand, K, fn, "cand");
+  TORCH_CHECK(cand.device() == q.device(), fn, ": cand must be on ", q.device());
+  int B = (int)q.size(0), E = (int)cand.size(0);
+  rank_vec(base, torch::kFloat32, B, q.device(), fn, "base");
+  rank_vec(counts, torch::kInt32, B, q.device(), fn, "counts");
+  if (B == 0 || E == 0) return;
+  if (q.is_cuda()) {
+    TORCH_CHECK(hip_available(), fn, ": CUDA tensor but no HIP device");
+    rank_count_gpu(cfp(q), cfp(cand), cfp(base), counts.data_ptr<int32_t>(), B, E, (int)K, qs,
+                   cs, (int)max_blocks, current_stream(q.device()));
+  } else {
+    rank_count_cpu(cfp(q), cfp(cand), cfp(base), counts.data_ptr<int32_t>(), B, E, (int)K, qs,
+                   cs);
+  }
+}
+
+// out[p] = dot_K(q[owner[p]], cand[p]); owner is the caller's int32 CPU
+// array, checked here and copied to the device of q.
+void pair_scores(torch::Tensor q, torch::Tensor cand, torch::Tensor owner, torch::Tensor out,
+                 int64_t K) {
+  const char* fn = "pair_scores";
+  TORCH_CHECK(K >= 1, fn, ": K must be >= 1");
+  int qs = rank_rows(q, K, fn, "q"), cs = rank_rows(cand, K, fn, "cand");
+  TORCH_CHECK(cand.device() == q.device(), fn, ": cand must be on ", q.device());
+  int B = (int)q.size(0), P = (int)cand.size(0);
+  rank_vec(owner, torch::kInt32, P, torch::Device(torch::kCPU), fn, "owner");
+  rank_vec(out, torch::kFloat32, P, q.device(), fn, "out");
+  const int32_t* op = owner.data_ptr<int32_t>();
+  for (int p = 0; p < P; ++p)
+    TORCH_CHECK(op[p] >= 0 && op[p] < B, fn, ": owner[", p, "] = ", op[p], " is not in [0, ", B,
+                ")");
+  if (P == 0) return;
+  if (q.is_cuda()) {
+    TORCH_CHECK(hip_available(), fn, ": CUDA tensor but no HIP device");
+    auto owner_d = owner.to(q.device());
+    pair_scores_gpu(cfp(q), cfp(cand), owner_d.data_ptr<int32_t>(), fp(out), P, (int)K, qs, cs,
+                    current_stream(q.device()));
+  } else {
+    pair_scores_cpu(cfp(q), cfp(cand), op, fp(out), P, (int)K, qs, cs);
+  }
+}
+
 // Grouped RESCAL step (GPU): triples pre-sorted by relation; group g =
 // triples [starts[g], starts[g+1]) sharing relation matrix rm[g]. The
 // three dim^2 products run as MFMA-tiled grouped GEMMs (U = S R,
@@ -4172,6 +4244,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rescal_step", &rescal_step, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_grouped", &rescal_step_grouped, py::call_guard<py::gil_scoped_release>());
   m.def("kge_complex_score", &kge_complex_score, py::call_guard<py::gil_scoped_release>());
+  m.def("rank_count", &rank_count, py::arg("q"), py::arg("cand"), py::arg("base"),
+        py::arg("counts"), py::arg("K"), py::arg("max_blocks") = 0,
+        py::call_guard<py::gil_scoped_release>());
+  m.def("pair_scores", &pair_scores, py::arg("q"), py::arg("cand"), py::arg("owner"),
+        py::arg("out"), py::arg("K"), py::call_guard<py::gil_scoped_release>());
   m.def("w2v_sgns_step", &w2v_sgns_step, py::call_guard<py::gil_scoped_release>());
   m.def("mf_update_step", &mf_update_step, py::call_guard<py::gil_scoped_release>());
   m.def("mf_loss", &mf_loss, py::call_guard<py::gil_scoped_release>());

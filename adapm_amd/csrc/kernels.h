@@ -225,6 +225,31 @@ namespace adapm {
 void kge_complex_score_mfma_gpu(const float* s, const float* r, const float* cand,
                                 float* scores, float* qbuf, int B, int E, int D, void* stream);
 
+// Rank counting for evaluation (k_mfma_rank_count): score a tile, count the
+// winners, write no score matrix.
+//   counts[b] += #{ e in [0, E) : dot_K(Q[b], C[e]) > base[b]  or  isnan(dot_K(Q[b], C[e])) }
+//   Q: [B] rows, row stride qstride >= K floats, first K used
+//   C: [E] rows, row stride cstride >= K floats, first K used
+//   base: [B] float    counts: [B] int32, accumulated (the caller zeroes it; chunks add up)
+// The comparison is strict: a score equal to base does not count. Any
+// K >= 1; row offsets are 64-bit. max_blocks caps the grid (0: the launcher's
+// own cap); a workgroup adds to a row of counts at most once. B < 1 or E < 1
+// is a no-op. The CPU twin sums each dot as a std::fmaf chain in ascending k.
+void rank_count_gpu(const float* Q, const float* C, const float* base, int32_t* counts, int B,
+                    int E, int K, int qstride, int cstride, int max_blocks, void* stream);
+void rank_count_cpu(const float* Q, const float* C, const float* base, int32_t* counts, int B,
+                    int E, int K, int qstride, int cstride);
+
+// Pair scores: out[p] = dot_K(Q[owner[p]], C[p]) for p in [0, P), owner int32
+// in [0, B). out[p] carries the bits of the score rank_count computes for
+// that (query, candidate) pair wherever the candidate sits in its tiles, so
+// a base taken from here never counts its own candidate, and a competitor is
+// above base here exactly when rank_count counted it.
+void pair_scores_gpu(const float* Q, const float* C, const int32_t* owner, float* out, int P,
+                     int K, int qstride, int cstride, void* stream);
+void pair_scores_cpu(const float* Q, const float* C, const int32_t* owner, float* out, int P,
+                     int K, int qstride, int cstride);
+
 // Batched varying-M grouped GEMM (triples sorted by relation; group g =
 // rows [starts[g], starts[g+1]), relation matrix g at Rm + g*rstride):
 //   mode 0: Out[row] = S_g @ R_g        (U = R^T e_s per row)

@@ -85,6 +85,32 @@ void kge_complex_score_cpu(const float* s, const float* r, const float* cand, fl
   }
 }
 
+// fp32 dot as an fmaf chain in ascending k: the order of the MFMA kernels
+static inline float dot_chain_(const float* q, const float* c, int K) {
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) acc = std::fmaf(q[k], c[k], acc);
+  return acc;
+}
+
+void rank_count_cpu(const float* Q, const float* C, const float* base, int32_t* counts, int B,
+                    int E, int K, int qstride, int cstride) {
+  for (int b = 0; b < B; ++b) {
+    const float* qb = Q + (int64_t)b * qstride;
+    int32_t n = 0;
+    for (int e = 0; e < E; ++e) {
+      float v = dot_chain_(qb, C + (int64_t)e * cstride, K);
+      n += (v > base[b] || std::isnan(v)) ? 1 : 0;
+    }
+    counts[b] += n;
+  }
+}
+
+void pair_scores_cpu(const float* Q, const float* C, const int32_t* owner, float* out, int P,
+                     int K, int qstride, int cstride) {
+  for (int p = 0; p < P; ++p)
+    out[p] = dot_chain_(Q + (int64_t)owner[p] * qstride, C + (int64_t)p * cstride, K);
+}
+
 void w2v_sgns_step_cpu(const float* ctr, const float* ctx, const float* neg, float* dctr,
                        float* dctx, float* dneg, float* loss, int B, int N, int D, float lr,
                        float eps) {

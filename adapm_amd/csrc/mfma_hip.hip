@@ -1,5 +1,5 @@
 // MFMA (matrix-core) kernels for the GEMM-shaped compute paths:
-// KGE full-entity eval scoring and grouped RESCAL products.
+// KGE full-entity eval scoring, rank counting and grouped RESCAL products.
 //
 // gfx950 keeps fp32-input MFMA (v_mfma_f32_16x16x4_f32): exact f32 at
 // the f32 vector rate, but ~2.4-2.8x a VALU f32 GEMM in practice (one
@@ -7,12 +7,18 @@
 // Shapes here are fp32 training state, so this is the right instrument
 // (no xf32 on gfx950; bf16 would change numerics).
 //
-// Tiling: one workgroup = 4 waves; each wave owns one 16x16 output tile
-// -> workgroup tile 16(M) x 64(N). A-tile (16 x KC) is staged in LDS
-// once per workgroup; B-tiles (64 x KC) staged per wave. KC = 32 with
-// +1 padding against bank conflicts. Lane mapping for
-// v_mfma_f32_16x16x4_f32: A[l&15][l>>4], B[l>>4][l&15], C/D col=l&15,
-// row=(l>>4)*4+reg.
+// Tiling. Lane mapping of v_mfma_f32_16x16x4_f32: A[l&15][l>>4],
+// B[l>>4][l&15], C/D col = l&15, row = (l>>4)*4 + reg. A workgroup is 4
+// waves throughout.
+//   k_mfma_scores, k_mfma_rank_count: workgroup tile 16 queries x 256
+//     candidates, each wave FOUR 16x16 accumulators over its 64-candidate
+//     strip. Query tile (16 x KC) and candidate tile (256 x KC) staged in
+//     LDS per K-chunk, KC = 16, rows padded by one float against bank
+//     conflicts.
+//   k_mfma_pair_scores: each wave one 16x16 accumulator whose diagonal
+//     holds 16 (query, candidate) pairs; same K-chunking.
+//   k_mfma_grouped: workgroup tile 16(M) x 64(N), one accumulator per
+//     wave, KC = 32.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 
@@ -120,6 +126,161 @@ void kge_complex_score_mfma_gpu(const float* s, const float* r, const float* can
   // query buffer is dense D
   hipLaunchKernelGGL(k_mfma_scores, dim3(blocks), dim3(MT), 0, st, qbuf, cand, scores, B, E, D,
                      D, D << 1);
+}
+
+// ---------------------------------------------------------------- rank counting
+//
+// counts[b] += #{ e : dot_K(Q[b], C[e]) > base[b] or the dot is NaN } with
+// the tiling of k_mfma_scores and no score matrix: the epilogue compares
+// the accumulators with base[row] in registers. A workgroup handles units
+// (query tile m, segment seg): it walks the candidate tiles seg, seg + segs,
+// ... of query tile m with its counts in registers, reduces them over the 16
+// lanes of a row group and the four waves, and issues one atomicAdd per row.
+// The launcher sizes the grid so that no workgroup meets a query tile twice
+// (gridDim.x == mtiles * segs, or segs == 1 and gridDim.x < mtiles): one
+// integer atomic per row per workgroup, whatever E is. Integer adds make the
+// result independent of their order. Units that run at the same time differ
+// in m first, so they share the candidate tile they stream.
+__global__ void k_mfma_rank_count(const float* __restrict__ Q, const float* __restrict__ C,
+                                  const float* __restrict__ base, int* __restrict__ counts,
+                                  int B, int E, int K, int qstride, int cstride, int segs) {
+  constexpr int KC = 16;
+  __shared__ float lq[16][KC + 1];
+  __shared__ float lc[256][KC + 1];
+  __shared__ int lcnt[MT / 64][16];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int mtiles = (B + 15) / 16;
+  const int ntiles = (E + 255) / 256;
+
+  for (int u = blockIdx.x; u < mtiles * segs; u += gridDim.x) {
+    const int m0 = (u % mtiles) * 16;
+    const int seg = u / mtiles;
+    float bs[4];
+    int cnt[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int row = m0 + ((lane >> 4) << 2) + r;
+      bs[r] = row < B ? base[row] : 0.f;  // rows >= B are dropped at the atomic
+    }
+    for (int nt = seg; nt < ntiles; nt += segs) {
+      const int n0 = nt * 256;
+      f32x4 acc[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f},
+                      {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+      for (int k0 = 0; k0 < K; k0 += KC) {
+        int kc = min(KC, K - k0);
+        // ragged K and rows past the edge are zero-padded: 0 * 0 changes no bits
+        for (int idx = threadIdx.x; idx < 16 * KC; idx += MT) {
+          int r = idx / KC, c = idx % KC;
+          lq[r][c] = (m0 + r < B && c < kc) ? Q[(int64_t)(m0 + r) * qstride + k0 + c] : 0.f;
+        }
+        for (int idx = threadIdx.x; idx < 256 * KC; idx += MT) {
+          int r = idx / KC, c = idx % KC;
+          lc[r][c] = (n0 + r < E && c < kc) ? C[(int64_t)(n0 + r) * cstride + k0 + c] : 0.f;
+        }
+        __syncthreads();
+        const int arow = lane & 15;
+        const int kk = lane >> 4;
+#pragma unroll
+        for (int ks = 0; ks < KC; ks += 4) {
+          float a = lq[arow][ks + kk];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            int brow = (wave << 6) | (j << 4) | (lane & 15);
+            acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, lc[brow][ks + kk], acc[j], 0, 0, 0);
+          }
+        }
+        __syncthreads();
+      }
+      // col = lane&15 within sub-tile j, row = (lane>>4)*4+reg
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const bool cok = n0 + (wave << 6) + (j << 4) + (lane & 15) < E;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[j][r];
+          cnt[r] += (cok && (v > bs[r] || v != v)) ? 1 : 0;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int c = cnt[r];
+      for (int off = 8; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);  // stays in the row group
+      if ((lane & 15) == 0) lcnt[wave][((lane >> 4) << 2) + r] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16 && m0 + (int)threadIdx.x < B) {
+      int t = lcnt[0][threadIdx.x] + lcnt[1][threadIdx.x] + lcnt[2][threadIdx.x] +
+              lcnt[3][threadIdx.x];
+      if (t) atomicAdd(&counts[m0 + threadIdx.x], t);
+    }
+    __syncthreads();  // lcnt is rewritten by the next unit
+  }
+}
+
+void rank_count_gpu(const float* Q, const float* C, const float* base, int32_t* counts, int B,
+                    int E, int K, int qstride, int cstride, int max_blocks, void* stream) {
+  if (B < 1 || E < 1) return;
+  constexpr int CAP = 2048;  // about what 256 CUs hold at ~17 KB of LDS per workgroup
+  const int G = max_blocks > 0 ? std::min(max_blocks, CAP) : CAP;
+  const int mtiles = (B + 15) / 16, ntiles = (E + 255) / 256;
+  const int segs = G >= mtiles ? std::min(ntiles, G / mtiles) : 1;
+  const int blocks = G >= mtiles ? mtiles * segs : G;
+  hipLaunchKernelGGL(k_mfma_rank_count, dim3(blocks), dim3(MT), 0, (hipStream_t)stream, Q, C,
+                     base, counts, B, E, K, qstride, cstride, segs);
+}
+
+// out[p] = dot_K(Q[owner[p]], C[p]). Each wave takes 16 pairs: query rows
+// owner[p0..p0+16) as the A tile, candidates p0..p0+16 as the B tile, and
+// keeps the diagonal of the 16x16 product. An MFMA output element depends
+// only on its own row of A and column of B, summed over k in the order of
+// k_mfma_rank_count (same KC, same slices, same zero padding), so out[p]
+// has the bits of the score that kernel compares, at any tile position.
+__global__ void k_mfma_pair_scores(const float* __restrict__ Q, const float* __restrict__ C,
+                                   const int* __restrict__ owner, float* __restrict__ out,
+                                   int P, int K, int qstride, int cstride) {
+  constexpr int KC = 16;
+  __shared__ float lq[64][KC + 1];
+  __shared__ float lc[64][KC + 1];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  for (int64_t p0 = (int64_t)blockIdx.x * 64; p0 < P; p0 += (int64_t)gridDim.x * 64) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k0 = 0; k0 < K; k0 += KC) {
+      int kc = min(KC, K - k0);
+      for (int idx = threadIdx.x; idx < 64 * KC; idx += MT) {
+        int r = idx / KC, c = idx % KC;
+        int64_t p = p0 + r;
+        bool ok = p < P && c < kc;
+        lq[r][c] = ok ? Q[(int64_t)owner[p] * qstride + k0 + c] : 0.f;
+        lc[r][c] = ok ? C[p * cstride + k0 + c] : 0.f;
+      }
+      __syncthreads();
+      const int row = (wave << 4) | (lane & 15);
+      const int kk = lane >> 4;
+#pragma unroll
+      for (int ks = 0; ks < KC; ks += 4)
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(lq[row][ks + kk], lc[row][ks + kk], acc, 0,
+                                                   0, 0);
+      __syncthreads();
+    }
+    // element (i, i): col = lane&15 = i, row = (lane>>4)*4 + reg = i
+    const int i = lane & 15;
+    int64_t p = p0 + (wave << 4) + i;
+    if ((i >> 2) == (lane >> 4) && p < P) {
+      int reg = i & 3;
+      out[p] = reg == 0 ? acc[0] : reg == 1 ? acc[1] : reg == 2 ? acc[2] : acc[3];
+    }
+  }
+}
+
+void pair_scores_gpu(const float* Q, const float* C, const int32_t* owner, float* out, int P,
+                     int K, int qstride, int cstride, void* stream) {
+  if (P < 1) return;
+  int blocks = (int)std::min<int64_t>(((int64_t)P + 63) / 64, 8192);
+  hipLaunchKernelGGL(k_mfma_pair_scores, dim3(blocks), dim3(MT), 0, (hipStream_t)stream, Q, C,
+                     owner, out, P, K, qstride, cstride);
 }
 
 // ---------------------------------------------------------------- grouped GEMMs

@@ -30,6 +30,7 @@ import adapm_amd
 from adapm_amd import _C
 
 from ._step import StepModel
+from .kge_eval import evaluate_ranks, format_ranks
 
 
 @dataclasses.dataclass
@@ -252,6 +253,27 @@ class ComplEx(StepModel):
             out["n"] = float(vec[0])
         return out
 
+    def _rank_layout(self):
+        return self.cfg.dim, self.cfg.row, self.cfg.dim, self.cfg.row
+
+    def _rank_query(self, side, s_v, r_v, o_v):
+        """psi = sum (s_re r_re - s_im r_im) o_re + (s_im r_re + s_re r_im) o_im
+        is linear in each of s, r, o: the query of a side holds the
+        coefficients of that side's [re | im] halves."""
+        dc = self.cfg.dim // 2
+        a, b = {"o": (s_v, r_v), "s": (r_v, o_v), "r": (s_v, o_v)}[side]
+        a_re, a_im, b_re, b_im = a[:, :dc], a[:, dc:2 * dc], b[:, :dc], b[:, dc:2 * dc]
+        if side == "o":
+            return torch.cat([a_re * b_re - a_im * b_im, a_im * b_re + a_re * b_im], dim=1)
+        return torch.cat([a_re * b_re + a_im * b_im, a_re * b_im - a_im * b_re], dim=1)
+
+    def evaluate_ranks(self, triples, filter_triples=None, sides="sro", hits_at=(1, 3, 10),
+                       chunk: int = 65536, return_ranks: bool = False) -> dict:
+        """Subject, relation and object ranks against ALL candidates, raw and
+        (s, o sides) filtered: kge_eval.evaluate_ranks."""
+        return evaluate_ranks(self, triples, filter_triples, sides, hits_at, chunk,
+                              return_ranks)
+
     @torch.no_grad()
     def evaluate(self, triples: np.ndarray, num_candidates: int = 1000,
                  hits_at=(1, 3, 10)) -> dict:
@@ -366,6 +388,9 @@ def main():
     ap.add_argument("--eval-triples", type=int, default=1024)
     ap.add_argument("--eval-full", action="store_true",
                     help="rank against ALL entities (reference eval)")
+    ap.add_argument("--eval-ranks", action="store_true",
+                    help="subject / relation / object ranks against ALL candidates, "
+                         "filtered and raw, printed as the reference's table")
     ap.add_argument("--checkpoint", type=str, default="")
     ap.add_argument("--device", type=str, default=None)
     a = ap.parse_args()
@@ -394,7 +419,11 @@ def main():
         total = worker.allreduce(float(np.mean(losses)))
         if rank == 0:
             print(f"[kge] epoch {ep}: loss {total / world:.4f} ({time.time()-t0:.1f}s)")
-        if a.eval_every and (ep + 1) % a.eval_every == 0:
+        if a.eval_every and (ep + 1) % a.eval_every == 0 and a.eval_ranks:
+            ev = model.evaluate_ranks(triples[:a.eval_triples], filter_triples=triples)
+            if rank == 0:
+                print(format_ranks(ev, prefix="[kge] eval"))
+        elif a.eval_every and (ep + 1) % a.eval_every == 0:
             ev = (model.evaluate_full(triples[:a.eval_triples], filter_triples=triples)
                   if a.eval_full else model.evaluate(triples[:a.eval_triples]))
             if rank == 0:
@@ -444,6 +473,29 @@ class Rescal(StepModel):
             self.worker.set(ks, v)
         self.worker.wait_sync()
         self.worker.barrier()
+
+    def _rank_layout(self):
+        D = self.cfg.dim
+        return D, 2 * D, D * D, 2 * D * D
+
+    def _rank_query(self, side, s_v, r_v, o_v):
+        """psi = s^T R o with R row-major: the object is scored by R^T s,
+        the subject by R o, the relation by outer(s, o) flattened."""
+        D = self.cfg.dim
+        s, o = s_v[:, :D], o_v[:, :D]
+        if side == "r":
+            return (s.unsqueeze(2) * o.unsqueeze(1)).reshape(-1, D * D)
+        Rm = r_v[:, :D * D].reshape(-1, D, D)
+        if side == "o":
+            return torch.bmm(s.unsqueeze(1), Rm).squeeze(1)
+        return torch.bmm(Rm, o.unsqueeze(2)).squeeze(2)
+
+    def evaluate_ranks(self, triples, filter_triples=None, sides="sro", hits_at=(1, 3, 10),
+                       chunk: int = 65536, return_ranks: bool = False) -> dict:
+        """Subject, relation and object ranks against ALL candidates, raw and
+        (s, o sides) filtered: kge_eval.evaluate_ranks."""
+        return evaluate_ranks(self, triples, filter_triples, sides, hits_at, chunk,
+                              return_ranks)
 
     def train_batch(self, triples: np.ndarray, sync_loss: bool = True,
                     grouped: bool = None):

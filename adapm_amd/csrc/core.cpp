@@ -3019,6 +3019,103 @@ class Server {
     return kge_step_fused_impl(keys_s, keys_r, keys_o, nullptr, &us, N, D, lr, eps);
   }
 
+  // The sides step (kernels.h: N object-side and NS subject-side negatives,
+  // gamma * E on the positive's rows) on the identity path. It follows
+  // kge_step_fused_impl pass for pass; what differs is the fifth key array,
+  // which needs no slot of its own in the row tags because all host keys are
+  // one staged blob and all drawn keys one device array, and that the
+  // arguments are checked before the store is, so that a bad call is refused
+  // on any store. A separate body rather than a flag in kge_step_fused_impl:
+  // that one stays as it is, statement for statement.
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_sides_fused_impl(
+      const torch::Tensor& keys_s, const torch::Tensor& keys_r, const torch::Tensor& keys_o,
+      const torch::Tensor* keys_neg_o, const torch::Tensor* keys_neg_s, UniformStream* us,
+      int64_t N, int64_t NS, int64_t D, double lr, double eps, double gamma_e,
+      double gamma_r) {
+    const char* name = us ? "kge_step_sides_fused_sampled" : "kge_step_sides_fused";
+    check_step_lanes(name, "D/2", D / 2);
+    TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+    const int64_t B = keys_s.numel();
+    TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B, name,
+                ": key arrays disagree on the batch");
+    // the tag pass numbers the occurrences in 32 bits, ROWTAG_SHARED aside
+    TORCH_CHECK(N < (int64_t)ROWTAG_SHARED && NS < (int64_t)ROWTAG_SHARED &&
+                    (3 + N + NS) * B < (int64_t)ROWTAG_SHARED,
+                name, ": too many keys in one step");
+    if (!us)
+      TORCH_CHECK(keys_neg_o->numel() == B * N && keys_neg_s->numel() == B * NS, name,
+                  ": key arrays disagree on the batch");
+    check_fused_identity(name, D);
+    HostKeys hk;
+    StagedKeys sk;
+    torch::Tensor drawn;
+    const int64_t *kno = nullptr, *kns = nullptr;
+    if (us) {
+      TORCH_CHECK(us->lo() >= 0 && us->hi() <= num_keys_, name, ": stream range [", us->lo(),
+                  ", ", us->hi(), ") exceeds the store's ", num_keys_, " keys");
+      TORCH_CHECK(us->device() == dev_, name, ": stream is not on the store's device");
+      TORCH_CHECK(B * (N + NS) > 0, name, ": nothing to draw");
+      hk = host_keys({&keys_s, &keys_r, &keys_o});
+      // one draw: the first B*N keys are object-side, the rest subject-side
+      drawn = us->draw(B * (N + NS));
+      kno = drawn.data_ptr<int64_t>();
+      kns = kno + B * N;
+    } else {
+      hk = host_keys({&keys_s, &keys_r, &keys_o, keys_neg_o, keys_neg_s});
+    }
+    const int64_t n_dev = us ? B * (N + NS) : 0;
+
+    auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    void* st = current_stream(dev_);
+    {
+      InflightGuard g(this);
+      std::unique_lock<std::mutex> mg(fused_mu_);  // see kge_step_fused_impl
+      const bool plain = fused_plain_ok(st);
+      uint32_t *tags = nullptr, *bits = nullptr;
+      if (plain) {
+        tags = reinterpret_cast<uint32_t*>(fused_tags_.data_ptr<int32_t>());
+        bits = tags + 32 * rowtag_words(num_keys_);
+      } else {
+        mg.unlock();
+      }
+      sk = upload_keys(name, hk, tags, kno, n_dev);
+      if (!us) kno = sk.ptr[3], kns = sk.ptr[4];
+      if (plain) {
+        RowTagKeys tk{{sk.ptr[0], kno, nullptr, nullptr}, {hk.blob.numel(), n_dev, 0, 0}, 2};
+        rowtag_flag_gpu(tags, tk, st);
+        rowtag_bits_gpu(tags, bits, tk, st);
+      }
+      kge_complex_step_sides_fused_gpu(
+          slab_.data, sk.ptr[0], sk.ptr[1], sk.ptr[2], kno, kns, loss.data_ptr<float>(), (int)B,
+          (int)N, (int)NS, (int)D, Slab::padded(uniform_len_), world_, (float)lr, (float)eps,
+          (float)gamma_e, (float)gamma_r, st, bits,
+          plain && fused_shared_stat_.defined()
+              ? reinterpret_cast<unsigned long long*>(fused_shared_stat_.data_ptr<int64_t>())
+              : nullptr);
+      (plain ? stat_fused_plain_ : stat_fused_atomic_) += 1;
+    }
+    count_fused_ops(3 * B + B * (N + NS));
+    return {loss, drawn};
+  }
+
+  torch::Tensor kge_step_sides_fused(torch::Tensor keys_s, torch::Tensor keys_r,
+                                     torch::Tensor keys_o, torch::Tensor keys_neg_o,
+                                     torch::Tensor keys_neg_s, int64_t N, int64_t NS, int64_t D,
+                                     double lr, double eps, double gamma_e, double gamma_r) {
+    return std::get<0>(kge_step_sides_fused_impl(keys_s, keys_r, keys_o, &keys_neg_o,
+                                                 &keys_neg_s, nullptr, N, NS, D, lr, eps,
+                                                 gamma_e, gamma_r));
+  }
+
+  // Returns (loss, the B*(N+NS) drawn keys on the device, object-side first).
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_sides_fused_sampled(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, UniformStream& us,
+      int64_t N, int64_t NS, int64_t D, double lr, double eps, double gamma_e,
+      double gamma_r) {
+    return kge_step_sides_fused_impl(keys_s, keys_r, keys_o, nullptr, nullptr, &us, N, NS, D,
+                                     lr, eps, gamma_e, gamma_r);
+  }
+
   // ---- fused slab-direct steps at world>1 / relocated layouts --------
   //
   // The identity-layout fused step above requires world==1. At world>1
@@ -3177,6 +3274,35 @@ class Server {
             kge_complex_step_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[1], res.ptr[2],
                                             res.ptr[3], loss, Bh, (int)N, (int)D, (float)lr,
                                             (float)eps);
+          }
+        });
+  }
+
+  // The sides step on the general path: five key arrays, of which the two
+  // negative ones may have no keys at all (N = 0 or NS = 0).
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_sides_fused_general(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, torch::Tensor keys_neg_o,
+      torch::Tensor keys_neg_s, int64_t N, int64_t NS, int64_t D, double lr, double eps,
+      double gamma_e, double gamma_r) {
+    const char* name = "kge_step_sides_fused";
+    TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+    TORCH_CHECK(uniform_len_ == 2 * D, name, ": store rows must be [emb|accum] = 2D");
+    if (dev_.is_cuda()) check_step_lanes(name, "D/2", D / 2);
+    return step_fused_general(
+        name,
+        {{&keys_s, 1}, {&keys_r, 1}, {&keys_o, 1}, {&keys_neg_o, N}, {&keys_neg_s, NS}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          if (dev_.is_cuda()) {
+            kge_complex_step_sides_fused_gpu(
+                slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], res.ptr[3], res.ptr[4], loss, Bh,
+                (int)N, (int)NS, (int)D, Slab::padded(uniform_len_), /*world=offsets-mode*/ 0,
+                (float)lr, (float)eps, (float)gamma_e, (float)gamma_r, current_stream(dev_));
+          } else {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            kge_complex_step_sides_fused_offs_cpu(
+                slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], res.ptr[3], res.ptr[4], loss, Bh,
+                (int)N, (int)NS, (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r);
           }
         });
   }
@@ -3802,6 +3928,43 @@ void kge_complex_step(torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::
   }
 }
 
+// ComplEx sides step (kernels.h): N object-side and NS subject-side negatives
+// per positive, gamma * E on the positive's rows. B is loss.numel(); every
+// tensor must have exactly the rows the step reads or writes.
+void kge_complex_step_sides(torch::Tensor s, torch::Tensor r, torch::Tensor o,
+                            torch::Tensor neg_o, torch::Tensor neg_s, torch::Tensor ds,
+                            torch::Tensor dr, torch::Tensor do_, torch::Tensor dneg_o,
+                            torch::Tensor dneg_s, torch::Tensor loss, int64_t N, int64_t NS,
+                            int64_t D, double lr, double eps, double gamma_e, double gamma_r) {
+  const char* name = "kge_complex_step_sides";
+  for (auto* t : {&s, &r, &o, &neg_o, &neg_s, &ds, &dr, &do_, &dneg_o, &dneg_s, &loss}) {
+    check_f32(*t, "kge tensor");
+    TORCH_CHECK(t->device() == s.device(), name, ": tensors on different devices");
+  }
+  TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+  TORCH_CHECK(D >= 2 && D % 2 == 0, name, ": D = ", D, " must be even and >= 2");
+  const int64_t B = loss.numel(), row = 2 * D;
+  for (auto* t : {&s, &r, &o, &ds, &dr, &do_})
+    TORCH_CHECK(t->numel() == B * row, name, ": s, r, o and their deltas must be [B][2D]");
+  for (auto* t : {&neg_o, &dneg_o})
+    TORCH_CHECK(t->numel() == B * N * row, name, ": neg_o and dneg_o must be [B*N][2D]");
+  for (auto* t : {&neg_s, &dneg_s})
+    TORCH_CHECK(t->numel() == B * NS * row, name, ": neg_s and dneg_s must be [B*NS][2D]");
+  if (s.is_cuda()) {
+    TORCH_CHECK(hip_available(), name, ": CUDA tensor but no HIP device");
+    check_step_lanes(name, "D/2", D / 2);
+    kge_complex_step_sides_gpu(cfp(s), cfp(r), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(dr),
+                               fp(do_), fp(dneg_o), fp(dneg_s), fp(loss), (int)B, (int)N,
+                               (int)NS, (int)D, (float)lr, (float)eps, (float)gamma_e,
+                               (float)gamma_r, current_stream(s.device()));
+  } else {
+    kge_complex_step_sides_cpu(cfp(s), cfp(r), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(dr),
+                               fp(do_), fp(dneg_o), fp(dneg_s), fp(loss), (int)B, (int)N,
+                               (int)NS, (int)D, (float)lr, (float)eps, (float)gamma_e,
+                               (float)gamma_r);
+  }
+}
+
 void rescal_step(torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::Tensor neg,
                  torch::Tensor ds, torch::Tensor drl, torch::Tensor do_, torch::Tensor dneg,
                  torch::Tensor loss, int64_t N, int64_t D, double lr, double eps) {
@@ -4240,6 +4403,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   using namespace adapm;
   m.def("hip_available", &hip_available);
   m.def("kge_complex_step", &kge_complex_step, py::call_guard<py::gil_scoped_release>());
+  m.def("kge_complex_step_sides", &kge_complex_step_sides,
+        py::call_guard<py::gil_scoped_release>());
   m.def("alias_draw", &alias_draw, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step", &rescal_step, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_grouped", &rescal_step_grouped, py::call_guard<py::gil_scoped_release>());
@@ -4311,6 +4476,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("w2v_step_fused", &Server::w2v_step_fused, py::call_guard<py::gil_scoped_release>())
       .def("mf_step_fused", &Server::mf_step_fused, py::call_guard<py::gil_scoped_release>())
       .def("kge_step_fused_general", &Server::kge_step_fused_general,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_sides_fused", &Server::kge_step_sides_fused,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_sides_fused_sampled", &Server::kge_step_sides_fused_sampled,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_sides_fused_general", &Server::kge_step_sides_fused_general,
            py::call_guard<py::gil_scoped_release>())
       .def("w2v_step_fused_general", &Server::w2v_step_fused_general,
            py::call_guard<py::gil_scoped_release>())

@@ -33,6 +33,33 @@ void kge_complex_step_cpu(const float* s, const float* r, const float* o, const 
                           float* ds, float* dr, float* do_, float* dneg, float* loss,
                           int B, int N, int D, float lr, float eps);
 
+// ComplEx SIDES step: the reference's two-sided objective with L2 on the
+// positive (reference knowledge_graph_embeddings.cc train(), ~:1106). One
+// work item is a positive (s, r, o) with N object-side negatives (s, r, o'_j)
+// and NS subject-side negatives (s'_j, r, o); each term is a logistic loss as
+// in the step above and loss[b] sums the 1 + N + NS of them.
+//  neg_o: [B*N][2D], neg_s: [B*NS][2D]; dneg_o, dneg_s likewise
+// Each row occurrence gets ONE AdaGrad update of its summed gradient:
+//  g_s = positive + N object-side terms + gamma_e * s
+//  g_o = positive + NS subject-side terms + gamma_e * o
+//  g_r = all 1 + N + NS terms + gamma_r * r
+//  o'_j, s'_j: their own term, no regulariser (the reference regularises
+//  positives only). The regulariser's value is not part of loss[b].
+// With NS = 0 and both gammas 0 this is kge_complex_step, in its order of
+// operations; the GPU launchers (classic and fused) then run the one-sided
+// kernel itself, which is what makes the results the same bit for bit. No
+// dropout (off by default in the reference).
+void kge_complex_step_sides_gpu(const float* s, const float* r, const float* o,
+                                const float* neg_o, const float* neg_s, float* ds, float* dr,
+                                float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
+                                int N, int NS, int D, float lr, float eps, float gamma_e,
+                                float gamma_r, void* stream);
+void kge_complex_step_sides_cpu(const float* s, const float* r, const float* o,
+                                const float* neg_o, const float* neg_s, float* ds, float* dr,
+                                float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
+                                int N, int NS, int D, float lr, float eps, float gamma_e,
+                                float gamma_r);
+
 // Row tags for the fused slab-direct steps: which key occurrences of one
 // batch share their slab row with another occurrence of the same batch.
 // `tags` is a device array of one word per row; its contents before a step
@@ -105,6 +132,22 @@ void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_
                                 int B, int N, int D, int32_t plen, int world, float lr,
                                 float eps, void* stream, const uint32_t* bits = nullptr,
                                 unsigned long long* shared_stat = nullptr);
+
+// FUSED sides step: kge_complex_step_sides on the slab's own rows, with the
+// addressing modes, the `bits` contract and shared_stat of
+// kge_complex_step_fused_gpu. The tags must cover all five key arrays.
+void kge_complex_step_sides_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
+                                      const int64_t* keys_o, const int64_t* keys_neg_o,
+                                      const int64_t* keys_neg_s, float* loss, int B, int N,
+                                      int NS, int D, int32_t plen, int world, float lr,
+                                      float eps, float gamma_e, float gamma_r, void* stream,
+                                      const uint32_t* bits = nullptr,
+                                      unsigned long long* shared_stat = nullptr);
+void kge_complex_step_sides_fused_offs_cpu(float* slab, const int64_t* offs_s,
+                                           const int64_t* offs_r, const int64_t* offs_o,
+                                           const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                           float* loss, int B, int N, int NS, int D, float lr,
+                                           float eps, float gamma_e, float gamma_r);
 
 // CPU tier of the offsets-mode fused steps (exercises the world>1 fused
 // protocol path in the gloo multi-process tests; serial, in-place).

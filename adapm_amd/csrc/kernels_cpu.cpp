@@ -65,6 +65,98 @@ void kge_complex_step_cpu(const float* s, const float* r, const float* o, const 
   }
 }
 
+// push-ready [delta | g^2] of one lane
+static inline void write_delta_(float* d_emb, float* d_acc, float g, float acc, float lr,
+                                float eps) {
+  *d_emb = -lr * g / std::sqrt(acc + g * g + eps);
+  *d_acc = g * g;
+}
+
+// Sides step (kernels.h): the object pass is kge_complex_step_cpu's loop
+// without the write of the positive object, the subject pass scores s'_j
+// against v = conj(r) * o.
+void kge_complex_step_sides_cpu(const float* s, const float* r, const float* o,
+                                const float* neg_o, const float* neg_s, float* ds, float* dr,
+                                float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
+                                int N, int NS, int D, float lr, float eps, float gamma_e,
+                                float gamma_r) {
+  const int dc = D >> 1;
+  const int row = D << 1;
+  std::vector<float> a_sre(dc), a_sim(dc), a_rre(dc), a_rim(dc), a_ore(dc), a_oim(dc);
+  std::vector<float> u_re(dc), u_im(dc), v_re(dc), v_im(dc);
+  for (int b = 0; b < B; ++b) {
+    const float* sb = s + (int64_t)b * row;
+    const float* rb = r + (int64_t)b * row;
+    const float* pb = o + (int64_t)b * row;
+    for (int k = 0; k < dc; ++k) {
+      u_re[k] = sb[k] * rb[k] - sb[dc + k] * rb[dc + k];
+      u_im[k] = sb[dc + k] * rb[k] + sb[k] * rb[dc + k];
+      a_sre[k] = a_sim[k] = a_rre[k] = a_rim[k] = 0.f;
+    }
+    float lsum = 0.f;
+    for (int j = 0; j <= N; ++j) {
+      const float* ob = (j == 0) ? pb : neg_o + ((int64_t)b * N + (j - 1)) * row;
+      float y = (j == 0) ? 1.f : -1.f;
+      double psi = 0.0;
+      for (int k = 0; k < dc; ++k) psi += u_re[k] * ob[k] + u_im[k] * ob[dc + k];
+      float c = -y * sigmoidf_(-y * (float)psi);
+      lsum += softplusf_(-y * (float)psi);
+      for (int k = 0; k < dc; ++k) {
+        float o_re = ob[k], o_im = ob[dc + k];
+        a_sre[k] += c * (rb[k] * o_re + rb[dc + k] * o_im);
+        a_sim[k] += c * (rb[k] * o_im - rb[dc + k] * o_re);
+        a_rre[k] += c * (sb[k] * o_re + sb[dc + k] * o_im);
+        a_rim[k] += c * (sb[k] * o_im - sb[dc + k] * o_re);
+        float g_re = c * u_re[k], g_im = c * u_im[k];
+        if (j == 0) {  // the positive object waits for the subject pass
+          a_ore[k] = g_re;
+          a_oim[k] = g_im;
+          continue;
+        }
+        float* dob = dneg_o + ((int64_t)b * N + (j - 1)) * row;
+        write_delta_(&dob[k], &dob[D + k], g_re, ob[D + k], lr, eps);
+        write_delta_(&dob[dc + k], &dob[D + dc + k], g_im, ob[D + dc + k], lr, eps);
+      }
+    }
+    for (int k = 0; k < dc; ++k) {
+      v_re[k] = rb[k] * pb[k] + rb[dc + k] * pb[dc + k];
+      v_im[k] = rb[k] * pb[dc + k] - rb[dc + k] * pb[k];
+    }
+    for (int j = 0; j < NS; ++j) {
+      const float* xb = neg_s + ((int64_t)b * NS + j) * row;
+      float* dxb = dneg_s + ((int64_t)b * NS + j) * row;
+      double psi = 0.0;
+      for (int k = 0; k < dc; ++k) psi += v_re[k] * xb[k] + v_im[k] * xb[dc + k];
+      float c = sigmoidf_((float)psi);
+      lsum += softplusf_((float)psi);
+      for (int k = 0; k < dc; ++k) {
+        float x_re = xb[k], x_im = xb[dc + k];
+        a_rre[k] += c * (x_re * pb[k] + x_im * pb[dc + k]);
+        a_rim[k] += c * (x_re * pb[dc + k] - x_im * pb[k]);
+        a_ore[k] += c * (x_re * rb[k] - x_im * rb[dc + k]);
+        a_oim[k] += c * (x_im * rb[k] + x_re * rb[dc + k]);
+        write_delta_(&dxb[k], &dxb[D + k], c * v_re[k], xb[D + k], lr, eps);
+        write_delta_(&dxb[dc + k], &dxb[D + dc + k], c * v_im[k], xb[D + dc + k], lr, eps);
+      }
+    }
+    float* dsb = ds + (int64_t)b * row;
+    float* drb = dr + (int64_t)b * row;
+    float* dpb = do_ + (int64_t)b * row;
+    for (int k = 0; k < dc; ++k) {
+      write_delta_(&dsb[k], &dsb[D + k], a_sre[k] + gamma_e * sb[k], sb[D + k], lr, eps);
+      write_delta_(&dsb[dc + k], &dsb[D + dc + k], a_sim[k] + gamma_e * sb[dc + k],
+                   sb[D + dc + k], lr, eps);
+      write_delta_(&drb[k], &drb[D + k], a_rre[k] + gamma_r * rb[k], rb[D + k], lr, eps);
+      write_delta_(&drb[dc + k], &drb[D + dc + k], a_rim[k] + gamma_r * rb[dc + k],
+                   rb[D + dc + k], lr, eps);
+      write_delta_(&dpb[k], &dpb[D + k], a_ore[k] + gamma_e * pb[k], pb[D + k], lr, eps);
+      write_delta_(&dpb[dc + k], &dpb[D + dc + k], a_oim[k] + gamma_e * pb[dc + k],
+                   pb[D + dc + k], lr, eps);
+    }
+    loss[b] = lsum;
+  }
+}
+
 void kge_complex_score_cpu(const float* s, const float* r, const float* cand, float* scores,
                            int B, int E, int D) {
   const int dc = D >> 1;
@@ -215,6 +307,86 @@ void kge_complex_step_fused_offs_cpu(float* slab, const int64_t* offs_s, const i
       adagrad_inplace(sb[dc + k], sb[D + dc + k], a_sim[k], lr, eps);
       adagrad_inplace(rb[k], rb[D + k], a_rre[k], lr, eps);
       adagrad_inplace(rb[dc + k], rb[D + dc + k], a_rim[k], lr, eps);
+    }
+    loss[b] = lsum;
+  }
+}
+
+// Sides step in place, in the order of k_kge_step_sides_fused: s and r are
+// read once, o'_j updated as they are scored, s updated between the passes,
+// the positive o read again for the subject pass, r and o updated last.
+void kge_complex_step_sides_fused_offs_cpu(float* slab, const int64_t* offs_s,
+                                           const int64_t* offs_r, const int64_t* offs_o,
+                                           const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                           float* loss, int B, int N, int NS, int D, float lr,
+                                           float eps, float gamma_e, float gamma_r) {
+  const int dc = D >> 1;
+  std::vector<float> a_sre(dc), a_sim(dc), a_rre(dc), a_rim(dc), a_ore(dc), a_oim(dc);
+  std::vector<float> u_re(dc), u_im(dc), v_re(dc), v_im(dc), sv(D), rv(D), pv(D);
+  for (int b = 0; b < B; ++b) {
+    float* sb = slab + offs_s[b];
+    float* rb = slab + offs_r[b];
+    float* pb = slab + offs_o[b];
+    std::copy(sb, sb + D, sv.begin());
+    std::copy(rb, rb + D, rv.begin());
+    for (int k = 0; k < dc; ++k) {
+      u_re[k] = sv[k] * rv[k] - sv[dc + k] * rv[dc + k];
+      u_im[k] = sv[dc + k] * rv[k] + sv[k] * rv[dc + k];
+      a_sre[k] = a_sim[k] = a_rre[k] = a_rim[k] = 0.f;
+    }
+    float lsum = 0.f;
+    for (int j = 0; j <= N; ++j) {
+      float* ob = (j == 0) ? pb : slab + offs_neg_o[(int64_t)b * N + (j - 1)];
+      float y = (j == 0) ? 1.f : -1.f;
+      float psi = 0.f;
+      for (int k = 0; k < dc; ++k) psi += u_re[k] * ob[k] + u_im[k] * ob[dc + k];
+      float c = -y * sigmoidf_(-y * psi);
+      lsum += softplusf_(-y * psi);
+      for (int k = 0; k < dc; ++k) {
+        float o_re = ob[k], o_im = ob[dc + k];
+        a_sre[k] += c * (rv[k] * o_re + rv[dc + k] * o_im);
+        a_sim[k] += c * (rv[k] * o_im - rv[dc + k] * o_re);
+        a_rre[k] += c * (sv[k] * o_re + sv[dc + k] * o_im);
+        a_rim[k] += c * (sv[k] * o_im - sv[dc + k] * o_re);
+        if (j == 0) {
+          a_ore[k] = c * u_re[k];
+          a_oim[k] = c * u_im[k];
+          continue;
+        }
+        adagrad_inplace(ob[k], ob[D + k], c * u_re[k], lr, eps);
+        adagrad_inplace(ob[dc + k], ob[D + dc + k], c * u_im[k], lr, eps);
+      }
+    }
+    for (int k = 0; k < dc; ++k) {
+      adagrad_inplace(sb[k], sb[D + k], a_sre[k] + gamma_e * sv[k], lr, eps);
+      adagrad_inplace(sb[dc + k], sb[D + dc + k], a_sim[k] + gamma_e * sv[dc + k], lr, eps);
+    }
+    std::copy(pb, pb + D, pv.begin());
+    for (int k = 0; k < dc; ++k) {
+      v_re[k] = rv[k] * pv[k] + rv[dc + k] * pv[dc + k];
+      v_im[k] = rv[k] * pv[dc + k] - rv[dc + k] * pv[k];
+    }
+    for (int j = 0; j < NS; ++j) {
+      float* xb = slab + offs_neg_s[(int64_t)b * NS + j];
+      float psi = 0.f;
+      for (int k = 0; k < dc; ++k) psi += v_re[k] * xb[k] + v_im[k] * xb[dc + k];
+      float c = sigmoidf_(psi);
+      lsum += softplusf_(psi);
+      for (int k = 0; k < dc; ++k) {
+        float x_re = xb[k], x_im = xb[dc + k];
+        a_rre[k] += c * (x_re * pv[k] + x_im * pv[dc + k]);
+        a_rim[k] += c * (x_re * pv[dc + k] - x_im * pv[k]);
+        a_ore[k] += c * (x_re * rv[k] - x_im * rv[dc + k]);
+        a_oim[k] += c * (x_im * rv[k] + x_re * rv[dc + k]);
+        adagrad_inplace(xb[k], xb[D + k], c * v_re[k], lr, eps);
+        adagrad_inplace(xb[dc + k], xb[D + dc + k], c * v_im[k], lr, eps);
+      }
+    }
+    for (int k = 0; k < dc; ++k) {
+      adagrad_inplace(rb[k], rb[D + k], a_rre[k] + gamma_r * rv[k], lr, eps);
+      adagrad_inplace(rb[dc + k], rb[D + dc + k], a_rim[k] + gamma_r * rv[dc + k], lr, eps);
+      adagrad_inplace(pb[k], pb[D + k], a_ore[k] + gamma_e * pv[k], lr, eps);
+      adagrad_inplace(pb[dc + k], pb[D + dc + k], a_oim[k] + gamma_e * pv[dc + k], lr, eps);
     }
     loss[b] = lsum;
   }

@@ -162,6 +162,164 @@ __global__ void k_kge_step(const float* __restrict__ s, const float* __restrict_
   }
 }
 
+// softplusf that keeps its relative accuracy where exp(x) is small: there
+// 1 + exp(x) rounds the whole term away (softplusf(-30) is 0, not 9.4e-14),
+// which shows once a sample's loss has no large term beside it. log1p as its
+// series below exp(x) = 0.01, where the next term is under 2.5e-9.
+__device__ inline float softplus1pf(float x) {
+  if (x > 20.f) return x;
+  float t = __expf(x);
+  return t < 0.01f ? t * (1.f - t * (0.5f - t * (1.f / 3.f))) : __logf(1.f + t);
+}
+
+// The sides step (kernels.h): the positive with N object-side and NS
+// subject-side negatives, and gamma * E on the positive's rows. Two passes per
+// workgroup. The object pass is k_kge_step's loop (u = s*r fixed) without the
+// write of the positive object; s is complete after it and is written there,
+// so that the subject pass (v = conj(r)*o fixed, psi = s'.v) holds r, o, v and
+// two accumulators, no more rows than the object pass does. r and o are
+// written at the end. __launch_bounds__(KT) lets KPT = 8 keep its rows in
+// registers.
+template <int KPT>
+__global__ void __launch_bounds__(KT)
+k_kge_step_sides(const float* __restrict__ s, const float* __restrict__ r,
+                 const float* __restrict__ o, const float* __restrict__ neg_o,
+                 const float* __restrict__ neg_s, float* __restrict__ ds,
+                 float* __restrict__ dr, float* __restrict__ do_, float* __restrict__ dneg_o,
+                 float* __restrict__ dneg_s, float* __restrict__ loss, int B, int N, int NS,
+                 int D, float lr, float eps, float gamma_e, float gamma_r) {
+  __shared__ float lds[KT / 64];
+  const int dc = D >> 1;
+  const int row = D << 1;  // floats per pulled row
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const float* sb = s + (int64_t)b * row;
+    const float* rb = r + (int64_t)b * row;
+    const float* pb = o + (int64_t)b * row;
+
+    float r_re[KPT], r_im[KPT], a_rre[KPT], a_rim[KPT];
+    float u_re[KPT], u_im[KPT];
+    float lsum = 0.f;
+    float c0 = 0.f;  // dL/dpsi of the positive
+    {
+      float s_re[KPT], s_im[KPT], a_sre[KPT], a_sim[KPT];
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        a_sre[i] = a_sim[i] = a_rre[i] = a_rim[i] = 0.f;
+        if (k < dc) {
+          s_re[i] = sb[k];
+          s_im[i] = sb[dc + k];
+          r_re[i] = rb[k];
+          r_im[i] = rb[dc + k];
+          u_re[i] = s_re[i] * r_re[i] - s_im[i] * r_im[i];
+          u_im[i] = s_im[i] * r_re[i] + s_re[i] * r_im[i];
+        } else {
+          s_re[i] = s_im[i] = r_re[i] = r_im[i] = u_re[i] = u_im[i] = 0.f;
+        }
+      }
+
+      // object pass: the positive (j = 0), then (s, r, o'_j)
+      for (int j = 0; j <= N; ++j) {
+        const float* ob = (j == 0) ? pb : neg_o + ((int64_t)b * N + (j - 1)) * row;
+        float y = (j == 0) ? 1.f : -1.f;
+        float part = 0.f;
+        float o_re[KPT], o_im[KPT];
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+          int k = threadIdx.x + i * KT;
+          o_re[i] = k < dc ? ob[k] : 0.f;
+          o_im[i] = k < dc ? ob[dc + k] : 0.f;
+          part += u_re[i] * o_re[i] + u_im[i] * o_im[i];
+        }
+        float psi = block_reduce_sum(part, lds);
+        float c = -y * sigmoidf(-y * psi);  // dL/dpsi, L = softplus(-y*psi)
+        if (threadIdx.x == 0) lsum += softplus1pf(-y * psi);
+        if (j == 0) c0 = c;
+
+        float* dob = (j == 0) ? nullptr : dneg_o + ((int64_t)b * N + (j - 1)) * row;
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+          int k = threadIdx.x + i * KT;
+          if (k >= dc) continue;
+          a_sre[i] += c * (r_re[i] * o_re[i] + r_im[i] * o_im[i]);
+          a_sim[i] += c * (r_re[i] * o_im[i] - r_im[i] * o_re[i]);
+          a_rre[i] += c * (s_re[i] * o_re[i] + s_im[i] * o_im[i]);
+          a_rim[i] += c * (s_re[i] * o_im[i] - s_im[i] * o_re[i]);
+          if (j == 0) continue;  // the positive object waits for the subject pass
+          write_delta(&dob[k], &dob[D + k], c * u_re[i], ob[D + k], lr, eps);
+          write_delta(&dob[dc + k], &dob[D + dc + k], c * u_im[i], ob[D + dc + k], lr, eps);
+        }
+      }
+
+      float* dsb = ds + (int64_t)b * row;
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        if (k >= dc) continue;
+        write_delta(&dsb[k], &dsb[D + k], a_sre[i] + gamma_e * s_re[i], sb[D + k], lr, eps);
+        write_delta(&dsb[dc + k], &dsb[D + dc + k], a_sim[i] + gamma_e * s_im[i],
+                    sb[D + dc + k], lr, eps);
+      }
+    }
+
+    // subject pass: (s'_j, r, o)
+    float p_re[KPT], p_im[KPT], a_ore[KPT], a_oim[KPT];
+    float v_re[KPT], v_im[KPT];
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      int k = threadIdx.x + i * KT;
+      p_re[i] = k < dc ? pb[k] : 0.f;
+      p_im[i] = k < dc ? pb[dc + k] : 0.f;
+      a_ore[i] = c0 * u_re[i];
+      a_oim[i] = c0 * u_im[i];
+      v_re[i] = r_re[i] * p_re[i] + r_im[i] * p_im[i];
+      v_im[i] = r_re[i] * p_im[i] - r_im[i] * p_re[i];
+    }
+    for (int j = 0; j < NS; ++j) {
+      const float* xb = neg_s + ((int64_t)b * NS + j) * row;
+      float* dxb = dneg_s + ((int64_t)b * NS + j) * row;
+      float part = 0.f;
+      float x_re[KPT], x_im[KPT];
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        x_re[i] = k < dc ? xb[k] : 0.f;
+        x_im[i] = k < dc ? xb[dc + k] : 0.f;
+        part += v_re[i] * x_re[i] + v_im[i] * x_im[i];
+      }
+      float psi = block_reduce_sum(part, lds);
+      float c = sigmoidf(psi);  // dL/dpsi, L = softplus(psi)
+      if (threadIdx.x == 0) lsum += softplus1pf(psi);
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        if (k >= dc) continue;
+        a_rre[i] += c * (x_re[i] * p_re[i] + x_im[i] * p_im[i]);
+        a_rim[i] += c * (x_re[i] * p_im[i] - x_im[i] * p_re[i]);
+        a_ore[i] += c * (x_re[i] * r_re[i] - x_im[i] * r_im[i]);
+        a_oim[i] += c * (x_im[i] * r_re[i] + x_re[i] * r_im[i]);
+        write_delta(&dxb[k], &dxb[D + k], c * v_re[i], xb[D + k], lr, eps);
+        write_delta(&dxb[dc + k], &dxb[D + dc + k], c * v_im[i], xb[D + dc + k], lr, eps);
+      }
+    }
+
+    float* drb = dr + (int64_t)b * row;
+    float* dpb = do_ + (int64_t)b * row;
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      int k = threadIdx.x + i * KT;
+      if (k >= dc) continue;
+      write_delta(&drb[k], &drb[D + k], a_rre[i] + gamma_r * r_re[i], rb[D + k], lr, eps);
+      write_delta(&drb[dc + k], &drb[D + dc + k], a_rim[i] + gamma_r * r_im[i], rb[D + dc + k],
+                  lr, eps);
+      write_delta(&dpb[k], &dpb[D + k], a_ore[i] + gamma_e * p_re[i], pb[D + k], lr, eps);
+      write_delta(&dpb[dc + k], &dpb[D + dc + k], a_oim[i] + gamma_e * p_im[i], pb[D + dc + k],
+                  lr, eps);
+    }
+    if (threadIdx.x == 0) loss[b] = lsum;
+  }
+}
+
 __global__ void k_kge_score(const float* __restrict__ s, const float* __restrict__ r,
                             const float* __restrict__ cand, float* __restrict__ scores, int B,
                             int E, int D) {
@@ -339,6 +497,26 @@ void kge_complex_step_gpu(const float* s, const float* r, const float* o, const 
     hipLaunchKernelGGL(k_kge_step<decltype(kpt)::value>, dim3(grid_for(B)), dim3(KT), 0,
                        (hipStream_t)stream, s, r, o, neg, ds, dr, do_, dneg, loss, B, N, D, lr,
                        eps);
+  });
+}
+void kge_complex_step_sides_gpu(const float* s, const float* r, const float* o,
+                                const float* neg_o, const float* neg_s, float* ds, float* dr,
+                                float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
+                                int N, int NS, int D, float lr, float eps, float gamma_e,
+                                float gamma_r, void* stream) {
+  if (B < 1) return;
+  // No subject side and no regulariser is the one-sided step, and is run by
+  // its kernel: the two kernels' object passes are the same expressions in the
+  // same order, but the compiler contracts them differently (acc + g*g is an
+  // fma in one and a mul and an add in the other), so only the same code
+  // gives the same bits.
+  if (NS == 0 && gamma_e == 0.f && gamma_r == 0.f)
+    return kge_complex_step_gpu(s, r, o, neg_o, ds, dr, do_, dneg_o, loss, B, N, D, lr, eps,
+                                stream);
+  dispatch_kpt(D >> 1, [&](auto kpt) {
+    hipLaunchKernelGGL(k_kge_step_sides<decltype(kpt)::value>, dim3(grid_for(B)), dim3(KT), 0,
+                       (hipStream_t)stream, s, r, o, neg_o, neg_s, ds, dr, do_, dneg_o, dneg_s,
+                       loss, B, N, NS, D, lr, eps, gamma_e, gamma_r);
   });
 }
 void kge_complex_score_gpu(const float* s, const float* r, const float* cand, float* scores,
@@ -894,6 +1072,194 @@ void kge_complex_step_fused_gpu(float* slab, const int64_t* keys_s, const int64_
                        dim3(grid_for(B)), dim3(KT), 0, (hipStream_t)stream, slab, keys_s, keys_r,
                        keys_o, keys_neg, loss, B, N, D, plen, world, lr, eps, bits,
                        shared_stat);
+  });
+}
+
+// One complex lane (re at k, im at dc + k) of a slab row through slab_adagrad.
+__device__ inline void slab_adagrad_complex(float* row, int k, int dc, int D, float g_re,
+                                            float g_im, float emb_re, float emb_im, float acc_re,
+                                            float acc_im, float lr, float eps, bool shared) {
+  slab_adagrad(&row[k], &row[D + k], g_re, emb_re, acc_re, lr, eps, shared);
+  slab_adagrad(&row[dc + k], &row[D + dc + k], g_im, emb_im, acc_im, lr, eps, shared);
+}
+
+// Fused sides step: k_kge_step_sides on the slab's own rows, with the
+// addressing and the UNIQ / bits contract of k_kge_step_fused. Every row is
+// written once per occurrence: o'_j and s'_j inside their pass, s between
+// the passes, r and the positive o at the end.
+template <int KPT, bool UNIQ>
+__global__ void __launch_bounds__(KT)
+k_kge_step_sides_fused(float* __restrict__ slab, const int64_t* __restrict__ keys_s,
+                       const int64_t* __restrict__ keys_r, const int64_t* __restrict__ keys_o,
+                       const int64_t* __restrict__ keys_neg_o,
+                       const int64_t* __restrict__ keys_neg_s, float* __restrict__ loss, int B,
+                       int N, int NS, int D, int32_t plen, int world, float lr, float eps,
+                       float gamma_e, float gamma_r, const uint32_t* __restrict__ bits,
+                       unsigned long long* __restrict__ shared_stat) {
+  __shared__ float lds[KT / 64];
+  const int dc = D >> 1;
+  const int w = UNIQ ? 1 : world;  // as in k_kge_step_fused
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const int64_t key_s = keys_s[b], key_r = keys_r[b], key_o = keys_o[b];
+    float* sb = row_at(slab, key_s, plen, w);
+    float* rb = row_at(slab, key_r, plen, w);
+    float* pb = row_at(slab, key_o, plen, w);
+    const bool s_shared = row_shared<UNIQ>(bits, key_s);
+    const bool r_shared = row_shared<UNIQ>(bits, key_r);
+    const bool p_shared = row_shared<UNIQ>(bits, key_o);
+    unsigned n_shared = (unsigned)s_shared + (unsigned)r_shared + (unsigned)p_shared;
+
+    float r_re[KPT], r_im[KPT], a_rre[KPT], a_rim[KPT];
+    float u_re[KPT], u_im[KPT];
+    float lsum = 0.f;
+    float c0 = 0.f;
+    {
+      float s_re[KPT], s_im[KPT], a_sre[KPT], a_sim[KPT];
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        a_sre[i] = a_sim[i] = a_rre[i] = a_rim[i] = 0.f;
+        if (k < dc) {
+          s_re[i] = sb[k];
+          s_im[i] = sb[dc + k];
+          r_re[i] = rb[k];
+          r_im[i] = rb[dc + k];
+          u_re[i] = s_re[i] * r_re[i] - s_im[i] * r_im[i];
+          u_im[i] = s_im[i] * r_re[i] + s_re[i] * r_im[i];
+        } else {
+          s_re[i] = s_im[i] = r_re[i] = r_im[i] = u_re[i] = u_im[i] = 0.f;
+        }
+      }
+
+      for (int j = 0; j <= N; ++j) {
+        const bool pos = j == 0;
+        const int64_t ok = pos ? key_o : keys_neg_o[(int64_t)b * N + (j - 1)];
+        float* ob = row_at(slab, ok, plen, w);
+        const bool o_shared = pos ? p_shared : row_shared<UNIQ>(bits, ok);
+        if (!pos) n_shared += (unsigned)o_shared;
+        float y = pos ? 1.f : -1.f;
+        float part = 0.f;
+        float o_re[KPT], o_im[KPT], Go_re[KPT], Go_im[KPT];
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+          int k = threadIdx.x + i * KT;
+          o_re[i] = k < dc ? ob[k] : 0.f;
+          o_im[i] = k < dc ? ob[dc + k] : 0.f;
+          Go_re[i] = (k < dc && !pos) ? ob[D + k] : 0.f;
+          Go_im[i] = (k < dc && !pos) ? ob[D + dc + k] : 0.f;
+          part += u_re[i] * o_re[i] + u_im[i] * o_im[i];
+        }
+        float psi = block_reduce_sum(part, lds);
+        float c = -y * sigmoidf(-y * psi);
+        if (threadIdx.x == 0) lsum += softplus1pf(-y * psi);
+        if (pos) c0 = c;
+
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+          int k = threadIdx.x + i * KT;
+          if (k >= dc) continue;
+          a_sre[i] += c * (r_re[i] * o_re[i] + r_im[i] * o_im[i]);
+          a_sim[i] += c * (r_re[i] * o_im[i] - r_im[i] * o_re[i]);
+          a_rre[i] += c * (s_re[i] * o_re[i] + s_im[i] * o_im[i]);
+          a_rim[i] += c * (s_re[i] * o_im[i] - s_im[i] * o_re[i]);
+          if (pos) continue;  // the positive object waits for the subject pass
+          slab_adagrad_complex(ob, k, dc, D, c * u_re[i], c * u_im[i], o_re[i], o_im[i],
+                               Go_re[i], Go_im[i], lr, eps, o_shared);
+        }
+      }
+
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        if (k >= dc) continue;
+        slab_adagrad_complex(sb, k, dc, D, a_sre[i] + gamma_e * s_re[i],
+                             a_sim[i] + gamma_e * s_im[i], s_re[i], s_im[i], sb[D + k],
+                             sb[D + dc + k], lr, eps, s_shared);
+      }
+    }
+
+    float p_re[KPT], p_im[KPT], a_ore[KPT], a_oim[KPT];
+    float v_re[KPT], v_im[KPT];
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      int k = threadIdx.x + i * KT;
+      p_re[i] = k < dc ? pb[k] : 0.f;
+      p_im[i] = k < dc ? pb[dc + k] : 0.f;
+      a_ore[i] = c0 * u_re[i];
+      a_oim[i] = c0 * u_im[i];
+      v_re[i] = r_re[i] * p_re[i] + r_im[i] * p_im[i];
+      v_im[i] = r_re[i] * p_im[i] - r_im[i] * p_re[i];
+    }
+    for (int j = 0; j < NS; ++j) {
+      const int64_t xk = keys_neg_s[(int64_t)b * NS + j];
+      float* xb = row_at(slab, xk, plen, w);
+      const bool x_shared = row_shared<UNIQ>(bits, xk);
+      n_shared += (unsigned)x_shared;
+      float part = 0.f;
+      float x_re[KPT], x_im[KPT], Gx_re[KPT], Gx_im[KPT];
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        x_re[i] = k < dc ? xb[k] : 0.f;
+        x_im[i] = k < dc ? xb[dc + k] : 0.f;
+        Gx_re[i] = k < dc ? xb[D + k] : 0.f;
+        Gx_im[i] = k < dc ? xb[D + dc + k] : 0.f;
+        part += v_re[i] * x_re[i] + v_im[i] * x_im[i];
+      }
+      float psi = block_reduce_sum(part, lds);
+      float c = sigmoidf(psi);
+      if (threadIdx.x == 0) lsum += softplus1pf(psi);
+#pragma unroll
+      for (int i = 0; i < KPT; ++i) {
+        int k = threadIdx.x + i * KT;
+        if (k >= dc) continue;
+        a_rre[i] += c * (x_re[i] * p_re[i] + x_im[i] * p_im[i]);
+        a_rim[i] += c * (x_re[i] * p_im[i] - x_im[i] * p_re[i]);
+        a_ore[i] += c * (x_re[i] * r_re[i] - x_im[i] * r_im[i]);
+        a_oim[i] += c * (x_im[i] * r_re[i] + x_re[i] * r_im[i]);
+        slab_adagrad_complex(xb, k, dc, D, c * v_re[i], c * v_im[i], x_re[i], x_im[i], Gx_re[i],
+                             Gx_im[i], lr, eps, x_shared);
+      }
+    }
+
+#pragma unroll
+    for (int i = 0; i < KPT; ++i) {
+      int k = threadIdx.x + i * KT;
+      if (k >= dc) continue;
+      slab_adagrad_complex(rb, k, dc, D, a_rre[i] + gamma_r * r_re[i],
+                           a_rim[i] + gamma_r * r_im[i], r_re[i], r_im[i], rb[D + k],
+                           rb[D + dc + k], lr, eps, r_shared);
+      slab_adagrad_complex(pb, k, dc, D, a_ore[i] + gamma_e * p_re[i],
+                           a_oim[i] + gamma_e * p_im[i], p_re[i], p_im[i], pb[D + k],
+                           pb[D + dc + k], lr, eps, p_shared);
+    }
+    if (threadIdx.x == 0) {
+      loss[b] = lsum;
+      if (UNIQ && shared_stat) atomicAdd(shared_stat, (unsigned long long)n_shared);
+    }
+  }
+}
+
+void kge_complex_step_sides_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
+                                      const int64_t* keys_o, const int64_t* keys_neg_o,
+                                      const int64_t* keys_neg_s, float* loss, int B, int N,
+                                      int NS, int D, int32_t plen, int world, float lr,
+                                      float eps, float gamma_e, float gamma_r, void* stream,
+                                      const uint32_t* bits, unsigned long long* shared_stat) {
+  if (B < 1) return;
+  // the one-sided step is run by its own kernel: see kge_complex_step_sides_gpu
+  if (NS == 0 && gamma_e == 0.f && gamma_r == 0.f)
+    return kge_complex_step_fused_gpu(slab, keys_s, keys_r, keys_o, keys_neg_o, loss, B, N, D,
+                                      plen, world, lr, eps, stream, bits, shared_stat);
+  const bool uniq = bits != nullptr && world == 1;  // as in kge_complex_step_fused_gpu
+  if (!uniq) bits = nullptr, shared_stat = nullptr;
+  dispatch_kpt(D >> 1, [&](auto kpt) {
+    constexpr int KPT = decltype(kpt)::value;
+    hipLaunchKernelGGL(
+        (uniq ? k_kge_step_sides_fused<KPT, true> : k_kge_step_sides_fused<KPT, false>),
+        dim3(grid_for(B)), dim3(KT), 0, (hipStream_t)stream, slab, keys_s, keys_r, keys_o,
+        keys_neg_o, keys_neg_s, loss, B, N, NS, D, plen, world, lr, eps, gamma_e, gamma_r, bits,
+        shared_stat);
   });
 }
 

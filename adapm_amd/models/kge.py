@@ -10,6 +10,10 @@ Rebuild of the reference app (reference apps/knowledge_graph_embeddings.cc):
     signal_intent_ahead, :1059-1123)
   - score/grad/AdaGrad: one fused device kernel per batch
     (kernels_hip.hip k_kge_step; reference :832-858, 415-435)
+  - the reference's two-sided objective, opt-in: subject-side negatives
+    and L2 on the positive's rows (neg_samples_subject, gamma_entity,
+    gamma_relation; k_kge_step_sides, reference train() and :1106).
+    Dropout is not built.
   - eval: MRR / Hits@k by scoring candidate sets (reference :544-712)
   - checkpoint: WaitSync -> Barrier -> rank-0 full pull -> save
     (reference :327-401)
@@ -45,6 +49,14 @@ class ComplExConfig:
     lookahead: int = 4        # batches of intent signaled ahead
     init_scale: float = 0.1
     seed: int = 42
+    # the sides step: any of these off its default selects it
+    neg_samples_subject: int = 0  # s-side negatives per positive
+    gamma_entity: float = 0.0     # L2 on the positive's s and o rows
+    gamma_relation: float = 0.0   # L2 on the positive's r row
+
+    @property
+    def sides(self) -> bool:
+        return bool(self.neg_samples_subject or self.gamma_entity or self.gamma_relation)
 
     @property
     def num_keys(self) -> int:
@@ -79,10 +91,29 @@ class ComplEx(StepModel):
         self.worker.intent(np.concatenate([s, r, o]), start, end)
 
     def _draw_negatives(self, B):
-        return self._negatives(B * self.cfg.neg_samples, self.cfg.num_entities)
+        """One draw per step. The sides step splits it: the first
+        B * neg_samples keys corrupt the object, the rest the subject."""
+        cfg = self.cfg
+        return self._negatives(B * (cfg.neg_samples + cfg.neg_samples_subject),
+                               cfg.num_entities)
+
+    def _neg_parts(self, neg_keys, B):
+        """The negative key arrays of the classic step, role by role."""
+        if not self.cfg.sides:
+            return [neg_keys]
+        n_o = B * self.cfg.neg_samples
+        return [neg_keys[:n_o], neg_keys[n_o:]]
+
+    def _sides_tail(self):
+        cfg = self.cfg
+        return (cfg.neg_samples, cfg.neg_samples_subject, cfg.dim, cfg.lr, cfg.eps,
+                cfg.gamma_entity, cfg.gamma_relation)
 
     def _launch(self, v, d, loss):
         cfg = self.cfg
+        if cfg.sides:  # v, d: s | r | o | neg_o | neg_s
+            _C.kge_complex_step_sides(*v, *d, loss, *self._sides_tail())
+            return
         _C.kge_complex_step(*v, *d, loss, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
 
     def train_batch(self, triples: np.ndarray, async_push: bool = True,
@@ -93,22 +124,37 @@ class ComplEx(StepModel):
         if neg_keys is None:
             neg_keys = self._draw_negatives(len(triples))
         t0 = self._ph("sample", t0)
-        handle = self._begin_step([*self.keys_of(triples), neg_keys])
+        handle = self._begin_step([*self.keys_of(triples),
+                                   *self._neg_parts(neg_keys, len(triples))])
         return self._finish_step(handle, self._launch, sync_loss, t0,
                                  wait_push=not async_push)
 
     def _classic_step(self, arrays):
+        if self.cfg.sides:
+            triples, negs_o, negs_s = arrays
+            return self.train_batch(triples, sync_loss=False, neg_keys=np.concatenate(
+                [negs_o.reshape(-1), negs_s.reshape(-1)]))
         triples, negs2 = arrays
         return self.train_batch(triples, sync_loss=False, neg_keys=negs2.reshape(-1))
 
     def _fused_identity_step(self, arrays):
-        return self._fused_raw(self.server.raw.kge_step_fused, arrays)
+        raw = self.server.raw
+        return self._fused_raw(
+            raw.kge_step_sides_fused if self.cfg.sides else raw.kge_step_fused, arrays)
 
     def _fused_general_step(self, arrays):
-        return self._fused_raw(self.server.raw.kge_step_fused_general, arrays)
+        raw = self.server.raw
+        return self._fused_raw(raw.kge_step_sides_fused_general if self.cfg.sides
+                               else raw.kge_step_fused_general, arrays)
 
     def _fused_raw(self, step, arrays):
         cfg = self.cfg
+        if cfg.sides:
+            triples, negs_o, negs_s = arrays
+            return step(*map(torch.from_numpy, self.keys_of(triples)),
+                        torch.from_numpy(np.ascontiguousarray(negs_o.reshape(-1))),
+                        torch.from_numpy(np.ascontiguousarray(negs_s.reshape(-1))),
+                        *self._sides_tail())
         triples, negs2 = arrays
         return step(*map(torch.from_numpy, self.keys_of(triples)),
                     torch.from_numpy(np.ascontiguousarray(negs2.reshape(-1))),
@@ -134,15 +180,24 @@ class ComplEx(StepModel):
             # negatives drawn on the device inside the step: the same keys
             # the host draw would give (ADAPM_HOST_NEGATIVES=1 keeps that
             # draw, for A/B runs)
-            NN = B * cfg.neg_samples
+            NN = B * (cfg.neg_samples + cfg.neg_samples_subject)
             sid = w.prepare_sample(NN, w.current_clock(), w.current_clock() + 2)
             us = smp.pull_device(w, sid, NN, draw=False)
             w.finish_sample(sid)
+            if cfg.sides:
+                loss, _neg = self.server.raw.kge_step_sides_fused_sampled(
+                    *map(torch.from_numpy, self.keys_of(triples)), us, *self._sides_tail())
+                return self._loss_out(loss, sync_loss)
             loss, _neg = self.server.raw.kge_step_fused_sampled(
                 *map(torch.from_numpy, self.keys_of(triples)),
                 us, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
             return self._loss_out(loss, sync_loss)
         negs2 = np.ascontiguousarray(self._draw_negatives(B), dtype=np.int64)
+        if cfg.sides:
+            n_o = B * cfg.neg_samples
+            return self._fused_step((triples, negs2[:n_o].reshape(B, cfg.neg_samples),
+                                     negs2[n_o:].reshape(B, cfg.neg_samples_subject)),
+                                    sync_loss, force_general)
         return self._fused_step((triples, negs2.reshape(B, cfg.neg_samples)),
                                 sync_loss, force_general)
 
@@ -153,8 +208,8 @@ class ComplEx(StepModel):
         reference's max_concurrent_loops pipelining): sample negatives,
         allocate buffers, issue one async pull. Returns a handle for
         train_prefetched."""
-        return self._begin_step([*self.keys_of(triples),
-                                 self._draw_negatives(len(triples))])
+        return self._begin_step([*self.keys_of(triples), *self._neg_parts(
+            self._draw_negatives(len(triples)), len(triples))])
 
     def train_prefetched(self, handle, sync_loss: bool = False):
         """Finish a prefetched batch: wait for the pull, run the step
@@ -380,6 +435,12 @@ def main():
     ap.add_argument("--relations", type=int, default=100)
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--neg", type=int, default=8)
+    ap.add_argument("--neg-samples-subject", type=int, default=0,
+                    help="subject-side negatives per positive (reference: as many as --neg)")
+    ap.add_argument("--gamma-entity", type=float, default=0.0,
+                    help="L2 on the positive's entity rows (reference: 1e-3)")
+    ap.add_argument("--gamma-relation", type=float, default=0.0,
+                    help="L2 on the positive's relation row (reference: 1e-3)")
     ap.add_argument("--triples", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--epochs", type=int, default=2)
@@ -400,7 +461,9 @@ def main():
     server.enable_sampling_support("local", True, "uniform", 0, a.entities)
     worker = _a.Worker(0, server)
     cfg = ComplExConfig(num_entities=a.entities, num_relations=a.relations, dim=a.dim,
-                        neg_samples=a.neg, batch_size=a.batch, lr=a.lr)
+                        neg_samples=a.neg, batch_size=a.batch, lr=a.lr,
+                        neg_samples_subject=a.neg_samples_subject,
+                        gamma_entity=a.gamma_entity, gamma_relation=a.gamma_relation)
     model = ComplEx(cfg, server, worker)
     model.init_embeddings()
     rank = server.my_rank()

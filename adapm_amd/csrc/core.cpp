@@ -4141,6 +4141,154 @@ torch::Tensor rescal_step_grouped(torch::Tensor s, torch::Tensor rm, torch::Tens
   return loss;
 }
 
+// What both RESCAL sides entry points check before anything runs: fp32,
+// contiguous, one device, the counts and gammas, and the entity-row tensors
+// against B, B*N, B*NS rows of 2D floats.
+static void check_rescal_sides(const char* name, const torch::Tensor& s, const torch::Tensor& o,
+                               const torch::Tensor& neg_o, const torch::Tensor& neg_s,
+                               const torch::Tensor& ds, const torch::Tensor& do_,
+                               const torch::Tensor& dneg_o, const torch::Tensor& dneg_s,
+                               std::initializer_list<const torch::Tensor*> others, int64_t B,
+                               int64_t N, int64_t NS, int64_t D, double gamma_e,
+                               double gamma_r) {
+  for (auto* t : {&s, &o, &neg_o, &neg_s, &ds, &do_, &dneg_o, &dneg_s}) {
+    check_f32(*t, "rescal sides tensor");
+    TORCH_CHECK(t->device() == s.device(), name, ": tensors on different devices");
+  }
+  for (auto* t : others) {
+    check_f32(*t, "rescal sides tensor");
+    TORCH_CHECK(t->device() == s.device(), name, ": tensors on different devices");
+  }
+  TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+  TORCH_CHECK(N <= INT32_MAX && NS <= INT32_MAX, name, ": too many negatives");
+  TORCH_CHECK(gamma_e >= 0 && gamma_r >= 0, name, ": gamma_e = ", gamma_e, " and gamma_r = ",
+              gamma_r, " must be >= 0");
+  TORCH_CHECK(D >= 1, name, ": D = ", D, " must be >= 1");
+  TORCH_CHECK(B >= 0 && B <= INT32_MAX / (2 * D) && B * (N + NS + 1) <= INT32_MAX, name,
+              ": batch too large");
+  const int64_t row = 2 * D;
+  for (auto* t : {&s, &o, &ds, &do_})
+    TORCH_CHECK(t->numel() == B * row, name, ": s, o and their deltas must be [B][2D]");
+  for (auto* t : {&neg_o, &dneg_o})
+    TORCH_CHECK(t->numel() == B * N * row, name, ": neg_o and dneg_o must be [B*N][2D]");
+  for (auto* t : {&neg_s, &dneg_s})
+    TORCH_CHECK(t->numel() == B * NS * row, name, ": neg_s and dneg_s must be [B*NS][2D]");
+}
+
+// RESCAL sides step (kernels.h): N object-side and NS subject-side negatives
+// per positive, gamma * E on the positive's rows. B is loss.numel(). With
+// NS = 0 and both gammas 0 it is rescal_step itself, bit for bit.
+void rescal_step_sides(torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::Tensor neg_o,
+                       torch::Tensor neg_s, torch::Tensor ds, torch::Tensor drl,
+                       torch::Tensor do_, torch::Tensor dneg_o, torch::Tensor dneg_s,
+                       torch::Tensor loss, int64_t N, int64_t NS, int64_t D, double lr,
+                       double eps, double gamma_e, double gamma_r) {
+  const char* name = "rescal_step_sides";
+  const int64_t B = loss.numel();
+  check_rescal_sides(name, s, o, neg_o, neg_s, ds, do_, dneg_o, dneg_s, {&r, &drl, &loss}, B, N,
+                     NS, D, gamma_e, gamma_r);
+  TORCH_CHECK(D <= 196, name, ": D = ", D, " must be <= 196 (R and six D-vectors staged in LDS)");
+  for (auto* t : {&r, &drl})
+    TORCH_CHECK(t->numel() == B * 2 * D * D, name, ": r and drl must be [B][2*D*D]");
+  if (NS == 0 && gamma_e == 0 && gamma_r == 0) {
+    rescal_step(s, r, o, neg_o, ds, drl, do_, dneg_o, loss, N, D, lr, eps);
+    return;
+  }
+  if (s.is_cuda()) {
+    TORCH_CHECK(hip_available(), name, ": CUDA tensor but no HIP device");
+    rescal_step_sides_gpu(cfp(s), cfp(r), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(drl),
+                          fp(do_), fp(dneg_o), fp(dneg_s), fp(loss), (int)B, (int)N, (int)NS,
+                          (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r,
+                          current_stream(s.device()));
+  } else {
+    rescal_step_sides_cpu(cfp(s), cfp(r), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(drl),
+                          fp(do_), fp(dneg_o), fp(dneg_s), fp(loss), (int)B, (int)N, (int)NS,
+                          (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r);
+  }
+}
+
+// Grouped RESCAL sides step (GPU): rescal_step_grouped's layout (triples
+// sorted by relation, group g = triples [starts[g], starts[g+1]) sharing
+// rm[g]) for the two-sided objective. k_mfma_grouped does the six dim^2
+// products, with o and Z standing in for its W and S operands:
+//   U = S R (mode 0), V = O R^T (mode 1); middle phase -> W, Z, c_0 u;
+//   dS_raw = W R^T (mode 1), dO_extra = Z R (mode 0),
+//   dR_a = S^T W, dR_b = Z^T O (mode 2),
+// and the AdaGrad epilogue sums the raw buffers and adds gamma * row, for drl
+// gamma_r * Bg * R_g: the group's gradient is summed over its Bg positives.
+// With NS = 0 and both gammas 0 it is rescal_step_grouped itself.
+torch::Tensor rescal_step_sides_grouped(torch::Tensor s, torch::Tensor rm, torch::Tensor o,
+                                        torch::Tensor neg_o, torch::Tensor neg_s,
+                                        torch::Tensor ds, torch::Tensor drl, torch::Tensor do_,
+                                        torch::Tensor dneg_o, torch::Tensor dneg_s,
+                                        torch::Tensor starts, int64_t N, int64_t NS, int64_t D,
+                                        double lr, double eps, double gamma_e, double gamma_r) {
+  const char* name = "rescal_step_sides_grouped";
+  TORCH_CHECK(D >= 1 && D % 4 == 0, name, ": D = ", D, " must be a positive multiple of 4");
+  TORCH_CHECK(D <= 8192, name, ": D = ", D, " is too large");
+  TORCH_CHECK(starts.scalar_type() == torch::kInt32 && starts.device().is_cpu() &&
+                  starts.is_contiguous() && starts.numel() >= 1,
+              name, ": starts must be a contiguous int32 CPU tensor of G + 1 offsets");
+  const int64_t G = starts.numel() - 1;
+  const int32_t* sp = starts.data_ptr<int32_t>();
+  TORCH_CHECK(sp[0] == 0, name, ": starts[0] must be 0");
+  for (int64_t g = 0; g < G; ++g)
+    TORCH_CHECK(sp[g + 1] >= sp[g], name, ": starts must not decrease");
+  const int64_t B = sp[G];
+  check_rescal_sides(name, s, o, neg_o, neg_s, ds, do_, dneg_o, dneg_s, {&rm, &drl}, B, N, NS,
+                     D, gamma_e, gamma_r);
+  for (auto* t : {&rm, &drl})
+    TORCH_CHECK(t->numel() == G * 2 * D * D, name, ": rm and drl must be [G][2*D*D]");
+  TORCH_CHECK(s.is_cuda(), name, " is the GPU path (CPU uses rescal_step_sides)");
+  TORCH_CHECK(hip_available(), name, ": CUDA tensor but no HIP device");
+  if (NS == 0 && gamma_e == 0 && gamma_r == 0)
+    return rescal_step_grouped(s, rm, o, neg_o, ds, drl, do_, dneg_o, starts, N, D, lr, eps);
+
+  auto dev = s.device();
+  auto opts = torch::TensorOptions().dtype(torch::kFloat32).device(dev);
+  auto loss = torch::empty({B}, opts);
+  // seven [B][D] buffers: U, V, W, Z, c_0 u, dS_raw, dO_extra
+  auto tmp = torch::empty({7, B * D}, opts);
+  float* U = tmp.data_ptr<float>();
+  float *V = U + B * D, *W = V + B * D, *Z = W + B * D, *dO0 = Z + B * D, *dSraw = dO0 + B * D,
+        *dOx = dSraw + B * D;
+  auto dR = torch::empty({2, G * D * D}, opts);
+  float* dRa = dR.data_ptr<float>();
+  float* dRb = dRa + G * D * D;
+  auto starts_d = starts.to(dev, /*non_blocking=*/true);
+  const int* sd = starts_d.data_ptr<int32_t>();
+  void* st = current_stream(dev);
+  const int iD = (int)D, e = (int)(2 * D), iG = (int)G;
+  const int64_t rs = 2 * D * D;
+  int64_t ntiles = (D + 63) / 64, tiles_bn = 0, tiles_dd = 0;
+  for (int64_t g = 0; g < G; ++g) {
+    tiles_bn += ((sp[g + 1] - sp[g] + 15) / 16) * ntiles;
+    tiles_dd += ((D + 15) / 16) * ntiles;
+  }
+  TORCH_CHECK(tiles_bn <= INT32_MAX && tiles_dd <= INT32_MAX, name, ": too many tiles");
+  const int tbn = (int)tiles_bn, tdd = (int)tiles_dd;
+  // U = S R, V = O R^T
+  mfma_grouped_gemm_gpu(cfp(s), W, cfp(rm), U, sd, iG, iD, e, iD, rs, iD, 0, 0, tbn, st);
+  mfma_grouped_gemm_gpu(cfp(s), cfp(o), cfp(rm), V, sd, iG, iD, e, e, rs, iD, 0, 1, tbn, st);
+  // scores, dneg_o, dneg_s, W, Z, c_0 u
+  rescal_mid_sides_gpu(U, V, cfp(o), cfp(neg_o), cfp(neg_s), fp(dneg_o), fp(dneg_s), W, Z, dO0,
+                       fp(loss), (int)B, (int)N, (int)NS, iD, (float)lr, (float)eps, st);
+  // ds from W R^T + gamma_e s
+  mfma_grouped_gemm_gpu(cfp(s), W, cfp(rm), dSraw, sd, iG, iD, e, iD, rs, iD, 0, 1, tbn, st);
+  adagrad_rows_sum_gpu(dSraw, nullptr, cfp(s), fp(ds), nullptr, B, iD, iD, 0, e, (float)lr,
+                       (float)eps, (float)gamma_e, st);
+  // do from c_0 u + Z R + gamma_e o
+  mfma_grouped_gemm_gpu(Z, W, cfp(rm), dOx, sd, iG, iD, iD, iD, rs, iD, 0, 0, tbn, st);
+  adagrad_rows_sum_gpu(dO0, dOx, cfp(o), fp(do_), nullptr, B, iD, iD, iD, e, (float)lr,
+                       (float)eps, (float)gamma_e, st);
+  // drl from S^T W + Z^T O + gamma_r Bg R_g
+  mfma_grouped_gemm_gpu(cfp(s), W, cfp(rm), dRa, sd, iG, iD, e, iD, rs, iD, D * D, 2, tdd, st);
+  mfma_grouped_gemm_gpu(Z, cfp(o), cfp(rm), dRb, sd, iG, iD, iD, e, rs, iD, D * D, 2, tdd, st);
+  adagrad_rows_sum_gpu(dRa, dRb, cfp(rm), fp(drl), sd, G, (int)(D * D), (int)(D * D),
+                       (int)(D * D), (int)(2 * D * D), (float)lr, (float)eps, (float)gamma_r, st);
+  return loss;
+}
+
 void w2v_sgns_step(torch::Tensor ctr, torch::Tensor ctx, torch::Tensor neg, torch::Tensor dctr,
                    torch::Tensor dctx, torch::Tensor dneg, torch::Tensor loss, int64_t N,
                    int64_t D, double lr, double eps) {
@@ -4408,6 +4556,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("alias_draw", &alias_draw, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step", &rescal_step, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_grouped", &rescal_step_grouped, py::call_guard<py::gil_scoped_release>());
+  m.def("rescal_step_sides", &rescal_step_sides, py::call_guard<py::gil_scoped_release>());
+  m.def("rescal_step_sides_grouped", &rescal_step_sides_grouped,
+        py::call_guard<py::gil_scoped_release>());
   m.def("kge_complex_score", &kge_complex_score, py::call_guard<py::gil_scoped_release>());
   m.def("rank_count", &rank_count, py::arg("q"), py::arg("cand"), py::arg("base"),
         py::arg("counts"), py::arg("K"), py::arg("max_blocks") = 0,

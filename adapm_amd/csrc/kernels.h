@@ -194,6 +194,34 @@ void rescal_step_cpu(const float* s, const float* r, const float* o, const float
                      float* ds, float* drl, float* do_, float* dneg, float* loss, int B, int N,
                      int D, float lr, float eps);
 
+// RESCAL SIDES step: the two-sided objective of the ComplEx sides step above
+// (the reference trains both scorers with one train()) for psi = s^T R o. One
+// work item is a positive (s, R, o) with N object-side negatives o'_j and NS
+// subject-side negatives s'_j; loss[b] sums the 1 + N + NS logistic terms and
+// leaves the regulariser's value out.
+//  neg_o: [B*N][2D], neg_s: [B*NS][2D]; dneg_o, dneg_s likewise
+// Factorisation, with u = R^T s and v = R o:
+//  object pass   c_0 = -sigmoid(-psi_0), c_j = sigmoid(psi_j), psi_j = u . o_j
+//                w = c_0 o + sum_j c_j o'_j          grad o'_j = c_j u
+//  subject pass  a_j = sigmoid(s'_j . v)
+//                z = sum_j a_j s'_j                  grad s'_j = a_j v
+//  positive      grad s = R w + gamma_e s
+//                grad o = c_0 u + R^T z + gamma_e o
+//                grad R = s w^T + z o^T + gamma_r R
+// so a sample costs ~6 D^2 + (N + NS) D. Each row occurrence gets ONE AdaGrad
+// update of its summed gradient; o is written after the subject pass. D <= 196
+// on the GPU (R and six D-vectors in LDS); callers check it. The bindings run
+// rescal_step itself when NS = 0 and both gammas are 0.
+void rescal_step_sides_gpu(const float* s, const float* r, const float* o, const float* neg_o,
+                           const float* neg_s, float* ds, float* drl, float* do_,
+                           float* dneg_o, float* dneg_s, float* loss, int B, int N, int NS,
+                           int D, float lr, float eps, float gamma_e, float gamma_r,
+                           void* stream);
+void rescal_step_sides_cpu(const float* s, const float* r, const float* o, const float* neg_o,
+                           const float* neg_s, float* ds, float* drl, float* do_,
+                           float* dneg_o, float* dneg_s, float* loss, int B, int N, int NS,
+                           int D, float lr, float eps, float gamma_e, float gamma_r);
+
 // word2vec SGNS step: per center/context pair with N negatives.
 //  ctr:  [B][2D] center (syn0) rows;  ctx: [B][2D] context (syn1) rows
 //  neg:  [B*N][2D] negative (syn1) rows
@@ -313,5 +341,25 @@ void rescal_mid_gpu(const float* U, const float* o, const float* neg, float* do_
 // raw-gradient buffer and the accumulator half of the pulled rows
 void adagrad_rows_gpu(const float* grad, const float* rows, float* out, int64_t n_rows,
                       int dvals, int gstride, int rstride, float lr, float eps, void* stream);
+
+// middle phase of the grouped RESCAL sides step, given U = S R (u_b) and
+// V = O R^T (v_b), both [B][D]. Object pass: scores u_b . o_j, dneg_o with
+// fused AdaGrad, Wm[b] = c_0 o + sum_j c_j o'_j, dO0[b] = c_0 u_b (the raw
+// gradient of the positive object so far). Subject pass: scores s'_j . v_b,
+// dneg_s with fused AdaGrad, Zm[b] = sum_j a_j s'_j. Wm, Zm, dO0 are [B][D].
+void rescal_mid_sides_gpu(const float* U, const float* V, const float* o, const float* neg_o,
+                          const float* neg_s, float* dneg_o, float* dneg_s, float* Wm,
+                          float* Zm, float* dO0, float* loss, int B, int N, int NS, int D,
+                          float lr, float eps, void* stream);
+
+// AdaGrad epilogue of a summed gradient: as adagrad_rows_gpu with
+//   g = ga[r][k] + gb[r][k] + gamma * count_r * rows[r][k]
+// gb may be null (no second buffer). count_r is starts[r+1] - starts[r] with
+// `starts` (device, n_rows + 1 ints), else 1; a row of count 0 gets [0 | 0].
+// `out` must not overlap ga or gb.
+void adagrad_rows_sum_gpu(const float* ga, const float* gb, const float* rows, float* out,
+                          const int* starts, int64_t n_rows, int dvals, int gastride,
+                          int gbstride, int rstride, float lr, float eps, float gamma,
+                          void* stream);
 
 }  // namespace adapm

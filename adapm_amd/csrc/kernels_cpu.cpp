@@ -568,4 +568,84 @@ void rescal_step_cpu(const float* s, const float* r, const float* o, const float
   }
 }
 
+// Sides step (kernels.h): rescal_step_cpu's object pass without the write of
+// the positive object, then the subject pass against v = R e_o.
+void rescal_step_sides_cpu(const float* s, const float* r, const float* o, const float* neg_o,
+                           const float* neg_s, float* ds, float* drl, float* do_,
+                           float* dneg_o, float* dneg_s, float* loss, int B, int N, int NS,
+                           int D, float lr, float eps, float gamma_e, float gamma_r) {
+  const int erow = 2 * D;
+  const int64_t rrow = 2LL * D * D;
+  std::vector<float> u(D), v(D), w(D), z(D);
+  for (int b = 0; b < B; ++b) {
+    const float* sb = s + (int64_t)b * erow;
+    const float* rb = r + (int64_t)b * rrow;
+    const float* pb = o + (int64_t)b * erow;
+    // u = R^T e_s, v = R e_o
+    for (int j = 0; j < D; ++j) {
+      double a = 0, c = 0;
+      for (int i = 0; i < D; ++i) {
+        a += rb[(int64_t)i * D + j] * sb[i];
+        c += rb[(int64_t)j * D + i] * pb[i];
+      }
+      u[j] = (float)a;
+      v[j] = (float)c;
+    }
+    std::fill(w.begin(), w.end(), 0.f);
+    std::fill(z.begin(), z.end(), 0.f);
+    float lsum = 0.f, c0 = 0.f;
+    for (int j = 0; j <= N; ++j) {
+      const float* ob = (j == 0) ? pb : neg_o + ((int64_t)b * N + j - 1) * erow;
+      float y = (j == 0) ? 1.f : -1.f;
+      double dot = 0;
+      for (int k = 0; k < D; ++k) dot += u[k] * ob[k];
+      float c = -y * sigmoidf_(-y * (float)dot);
+      lsum += softplusf_(-y * (float)dot);
+      for (int k = 0; k < D; ++k) w[k] += c * ob[k];
+      if (j == 0) {  // the positive object waits for the subject pass
+        c0 = c;
+        continue;
+      }
+      float* dob = dneg_o + ((int64_t)b * N + j - 1) * erow;
+      for (int k = 0; k < D; ++k) write_delta_(&dob[k], &dob[D + k], c * u[k], ob[D + k], lr, eps);
+    }
+    for (int j = 0; j < NS; ++j) {
+      const float* xb = neg_s + ((int64_t)b * NS + j) * erow;
+      float* dxb = dneg_s + ((int64_t)b * NS + j) * erow;
+      double dot = 0;
+      for (int k = 0; k < D; ++k) dot += v[k] * xb[k];
+      float a = sigmoidf_((float)dot);
+      lsum += softplusf_((float)dot);
+      for (int k = 0; k < D; ++k) {
+        z[k] += a * xb[k];
+        write_delta_(&dxb[k], &dxb[D + k], a * v[k], xb[D + k], lr, eps);
+      }
+    }
+    loss[b] = lsum;
+    // de_s = R w + gamma_e e_s, de_o = c0 u + R^T z + gamma_e e_o
+    float* dsb = ds + (int64_t)b * erow;
+    float* dpb = do_ + (int64_t)b * erow;
+    for (int i = 0; i < D; ++i) {
+      double a = 0, c = 0;
+      for (int k = 0; k < D; ++k) {
+        a += rb[(int64_t)i * D + k] * w[k];
+        c += rb[(int64_t)k * D + i] * z[k];
+      }
+      write_delta_(&dsb[i], &dsb[D + i], (float)a + gamma_e * sb[i], sb[D + i], lr, eps);
+      write_delta_(&dpb[i], &dpb[D + i], c0 * u[i] + (float)c + gamma_e * pb[i], pb[D + i], lr,
+                   eps);
+    }
+    // dR = e_s w^T + z e_o^T + gamma_r R
+    float* drb = drl + (int64_t)b * rrow;
+    for (int i = 0; i < D; ++i) {
+      for (int k = 0; k < D; ++k) {
+        int64_t idx = (int64_t)i * D + k;
+        write_delta_(&drb[idx], &drb[(int64_t)D * D + idx],
+                     sb[i] * w[k] + z[i] * pb[k] + gamma_r * rb[idx], rb[(int64_t)D * D + idx],
+                     lr, eps);
+      }
+    }
+  }
+}
+
 }  // namespace adapm

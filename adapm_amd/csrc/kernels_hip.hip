@@ -761,6 +761,136 @@ void rescal_step_gpu(const float* s, const float* r, const float* o, const float
                      s, r, o, neg, ds, drl, do_, dneg, loss, B, N, D, lr, eps);
 }
 
+// RESCAL sides step (kernels.h): k_rescal_step's shape, one workgroup per
+// positive with R in LDS, and beside R the six D-vectors u = R^T s, w, e_s,
+// v = R o, z, e_o. The object pass fills w and writes the o'_j, the subject
+// pass fills z and writes the s'_j; the positive's s, o and R are written
+// after both, since o's gradient needs z.
+__global__ void __launch_bounds__(KT)
+k_rescal_step_sides(const float* __restrict__ s, const float* __restrict__ r,
+                    const float* __restrict__ o, const float* __restrict__ neg_o,
+                    const float* __restrict__ neg_s, float* __restrict__ ds,
+                    float* __restrict__ drl, float* __restrict__ do_,
+                    float* __restrict__ dneg_o, float* __restrict__ dneg_s,
+                    float* __restrict__ loss, int B, int N, int NS, int D, float lr, float eps,
+                    float gamma_e, float gamma_r) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* Rm = smem;            // D*D
+  float* u = Rm + D * D;       // D
+  float* w = u + D;            // D
+  float* es = w + D;           // D
+  float* v = es + D;           // D
+  float* z = v + D;            // D
+  float* eo = z + D;           // D
+  float* red = eo + D;         // KT/64 reduction scratch
+  const int erow = 2 * D;
+  const int64_t rrow = 2LL * D * D;
+
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const float* sb = s + (int64_t)b * erow;
+    const float* rb = r + (int64_t)b * rrow;
+    const float* pb = o + (int64_t)b * erow;
+    for (int i = threadIdx.x; i < D * D; i += KT) Rm[i] = rb[i];
+    for (int i = threadIdx.x; i < D; i += KT) {
+      es[i] = sb[i];
+      eo[i] = pb[i];
+      w[i] = 0.f;
+      z[i] = 0.f;
+    }
+    __syncthreads();
+    // u = R^T e_s (thread j: column j), v = R e_o (thread j: row j)
+    for (int j = threadIdx.x; j < D; j += KT) {
+      float a = 0.f, c = 0.f;
+      for (int i = 0; i < D; ++i) {
+        a += Rm[i * D + j] * es[i];
+        c += Rm[j * D + i] * eo[i];
+      }
+      u[j] = a;
+      v[j] = c;
+    }
+    __syncthreads();
+
+    float lsum = 0.f;
+    float c0 = 0.f;  // dL/dpsi of the positive
+    // object pass: the positive (j = 0), then (s, R, o'_j)
+    for (int j = 0; j <= N; ++j) {
+      const float* ob = (j == 0) ? pb : neg_o + ((int64_t)b * N + j - 1) * erow;
+      float y = (j == 0) ? 1.f : -1.f;
+      float part = 0.f;
+      for (int k = threadIdx.x; k < D; k += KT) part += u[k] * ob[k];
+      float dot = block_reduce_sum(part, red);
+      float c = -y * sigmoidf(-y * dot);
+      if (threadIdx.x == 0) lsum += softplus1pf(-y * dot);
+      if (j == 0) {  // the positive object waits for the subject pass
+        c0 = c;
+        for (int k = threadIdx.x; k < D; k += KT) w[k] += c * ob[k];
+        continue;
+      }
+      float* dob = dneg_o + ((int64_t)b * N + j - 1) * erow;
+      for (int k = threadIdx.x; k < D; k += KT) {
+        w[k] += c * ob[k];  // single writer per k: thread-private index
+        write_delta(&dob[k], &dob[D + k], c * u[k], ob[D + k], lr, eps);
+      }
+    }
+    // subject pass: (s'_j, R, o)
+    for (int j = 0; j < NS; ++j) {
+      const float* xb = neg_s + ((int64_t)b * NS + j) * erow;
+      float* dxb = dneg_s + ((int64_t)b * NS + j) * erow;
+      float part = 0.f;
+      for (int k = threadIdx.x; k < D; k += KT) part += v[k] * xb[k];
+      float dot = block_reduce_sum(part, red);
+      float a = sigmoidf(dot);
+      if (threadIdx.x == 0) lsum += softplus1pf(dot);
+      for (int k = threadIdx.x; k < D; k += KT) {
+        z[k] += a * xb[k];
+        write_delta(&dxb[k], &dxb[D + k], a * v[k], xb[D + k], lr, eps);
+      }
+    }
+    if (threadIdx.x == 0) loss[b] = lsum;
+    __syncthreads();  // w and z complete
+
+    // de_s = R w + gamma_e e_s, de_o = c0 u + R^T z + gamma_e e_o
+    float* dsb = ds + (int64_t)b * erow;
+    float* dpb = do_ + (int64_t)b * erow;
+    for (int i = threadIdx.x; i < D; i += KT) {
+      float a = 0.f, c = 0.f;
+      for (int k = 0; k < D; ++k) {
+        a += Rm[i * D + k] * w[k];
+        c += Rm[k * D + i] * z[k];
+      }
+      write_delta(&dsb[i], &dsb[D + i], a + gamma_e * es[i], sb[D + i], lr, eps);
+      write_delta(&dpb[i], &dpb[D + i], c0 * u[i] + c + gamma_e * eo[i], pb[D + i], lr, eps);
+    }
+    // dR = e_s w^T + z e_o^T + gamma_r R
+    float* drb = drl + (int64_t)b * rrow;
+    for (int idx = threadIdx.x; idx < D * D; idx += KT) {
+      int i = idx / D, k = idx % D;
+      const int64_t acc = (int64_t)D * D + idx;
+      write_delta(&drb[idx], &drb[acc], es[i] * w[k] + z[i] * eo[k] + gamma_r * Rm[idx],
+                  rb[acc], lr, eps);
+    }
+    __syncthreads();
+  }
+}
+
+// floats of LDS k_rescal_step_sides uses at dimension D: R, six D-vectors
+// and the reduction scratch (158,384 B at D = 196, of 163,840 B a workgroup
+// may declare)
+static inline size_t rescal_sides_lds_bytes(int D) {
+  return ((size_t)D * D + 6 * (size_t)D + KT / 64) * sizeof(float);
+}
+
+void rescal_step_sides_gpu(const float* s, const float* r, const float* o, const float* neg_o,
+                           const float* neg_s, float* ds, float* drl, float* do_,
+                           float* dneg_o, float* dneg_s, float* loss, int B, int N, int NS,
+                           int D, float lr, float eps, float gamma_e, float gamma_r,
+                           void* stream) {
+  if (B < 1) return;
+  hipLaunchKernelGGL(k_rescal_step_sides, dim3(grid_for(B, 8192)), dim3(KT),
+                     rescal_sides_lds_bytes(D), (hipStream_t)stream, s, r, o, neg_o, neg_s, ds,
+                     drl, do_, dneg_o, dneg_s, loss, B, N, NS, D, lr, eps, gamma_e, gamma_r);
+}
+
 }  // namespace adapm
 
 namespace adapm {

@@ -481,4 +481,149 @@ void adagrad_rows_gpu(const float* grad, const float* rows, float* out, int64_t 
                      rows, out, n_rows, dvals, gstride, rstride, lr, eps);
 }
 
+// ---------------------------------------------------------------- grouped sides step
+//
+// The two-sided RESCAL objective (kernels.h, rescal_step_sides) on the grouped
+// path: k_mfma_grouped does all six dim^2 products, the two kernels below the
+// rest.
+
+// softplus1pf of kernels_hip.hip, repeated: log(1 + exp(x)) that keeps its
+// relative accuracy where exp(x) is small (log1p as its series below 0.01).
+__device__ inline float mid_softplus1pf(float x) {
+  if (x > 20.f) return x;
+  float t = __expf(x);
+  return t < 0.01f ? t * (1.f - t * (0.5f - t * (1.f / 3.f))) : __logf(1.f + t);
+}
+
+__device__ inline float mid_block_sum(float part, float* red) {
+  for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
+  int wv = threadIdx.x >> 6, ln = threadIdx.x & 63;
+  if (ln == 0) red[wv] = part;
+  __syncthreads();
+  float dot = (threadIdx.x < MT / 64) ? red[threadIdx.x] : 0.f;
+  if (threadIdx.x < 64)
+    for (int off = 2; off > 0; off >>= 1) dot += __shfl_xor(dot, off, 64);
+  if (threadIdx.x == 0) red[0] = dot;
+  __syncthreads();
+  dot = red[0];
+  __syncthreads();
+  return dot;
+}
+
+// Two passes per triple. Object pass: k_rescal_mid's loop, except that the
+// positive object's gradient so far, c_0 u, goes to dO0 unconverted (R^T z and
+// gamma_e o are still to come). Subject pass: the same against v, into Zm.
+// Every thread owns the indices k = tid + i*MT of Wm[b] and Zm[b], so their
+// running sums need no barrier.
+__global__ void __launch_bounds__(MT)
+k_rescal_mid_sides(const float* __restrict__ U, const float* __restrict__ V,
+                   const float* __restrict__ o, const float* __restrict__ neg_o,
+                   const float* __restrict__ neg_s, float* __restrict__ dneg_o,
+                   float* __restrict__ dneg_s, float* __restrict__ Wm, float* __restrict__ Zm,
+                   float* __restrict__ dO0, float* __restrict__ loss, int B, int N, int NS,
+                   int D, float lr, float eps) {
+  __shared__ float red[MT / 64];
+  const int erow = 2 * D;
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const float* ub = U + (int64_t)b * D;
+    const float* vb = V + (int64_t)b * D;
+    const float* pb = o + (int64_t)b * erow;
+    float* wb = Wm + (int64_t)b * D;
+    float* zb = Zm + (int64_t)b * D;
+    float* gb = dO0 + (int64_t)b * D;
+    float lsum = 0.f;
+    {  // the positive
+      float part = 0.f;
+      for (int k = threadIdx.x; k < D; k += MT) part += ub[k] * pb[k];
+      float dot = mid_block_sum(part, red);
+      float c = -1.f / (1.f + __expf(dot));
+      if (threadIdx.x == 0) lsum += mid_softplus1pf(-dot);
+      for (int k = threadIdx.x; k < D; k += MT) {
+        wb[k] = c * pb[k];
+        gb[k] = c * ub[k];
+        zb[k] = 0.f;
+      }
+    }
+    for (int j = 0; j < N; ++j) {
+      const float* ob = neg_o + ((int64_t)b * N + j) * erow;
+      float* dob = dneg_o + ((int64_t)b * N + j) * erow;
+      float part = 0.f;
+      for (int k = threadIdx.x; k < D; k += MT) part += ub[k] * ob[k];
+      float dot = mid_block_sum(part, red);
+      float c = 1.f / (1.f + __expf(-dot));
+      if (threadIdx.x == 0) lsum += mid_softplus1pf(dot);
+      for (int k = threadIdx.x; k < D; k += MT) {
+        wb[k] += c * ob[k];
+        float g = c * ub[k];
+        dob[k] = -lr * g * __frsqrt_rn(ob[D + k] + g * g + eps);
+        dob[D + k] = g * g;
+      }
+    }
+    for (int j = 0; j < NS; ++j) {
+      const float* xb = neg_s + ((int64_t)b * NS + j) * erow;
+      float* dxb = dneg_s + ((int64_t)b * NS + j) * erow;
+      float part = 0.f;
+      for (int k = threadIdx.x; k < D; k += MT) part += vb[k] * xb[k];
+      float dot = mid_block_sum(part, red);
+      float a = 1.f / (1.f + __expf(-dot));
+      if (threadIdx.x == 0) lsum += mid_softplus1pf(dot);
+      for (int k = threadIdx.x; k < D; k += MT) {
+        zb[k] += a * xb[k];
+        float g = a * vb[k];
+        dxb[k] = -lr * g * __frsqrt_rn(xb[D + k] + g * g + eps);
+        dxb[D + k] = g * g;
+      }
+    }
+    if (threadIdx.x == 0) loss[b] = lsum;
+  }
+}
+
+void rescal_mid_sides_gpu(const float* U, const float* V, const float* o, const float* neg_o,
+                          const float* neg_s, float* dneg_o, float* dneg_s, float* Wm,
+                          float* Zm, float* dO0, float* loss, int B, int N, int NS, int D,
+                          float lr, float eps, void* stream) {
+  if (B < 1) return;
+  hipLaunchKernelGGL(k_rescal_mid_sides, dim3(std::min(B, 8192)), dim3(MT), 0,
+                     (hipStream_t)stream, U, V, o, neg_o, neg_s, dneg_o, dneg_s, Wm, Zm, dO0,
+                     loss, B, N, NS, D, lr, eps);
+}
+
+// k_adagrad_rows of g = ga + gb + gamma * count * row (kernels.h)
+__global__ void k_adagrad_rows_sum(const float* __restrict__ ga, const float* __restrict__ gb,
+                                   const float* __restrict__ rows, float* __restrict__ out,
+                                   const int* __restrict__ starts, int64_t n_rows, int dvals,
+                                   int gastride, int gbstride, int rstride, float lr, float eps,
+                                   float gamma) {
+  int64_t total = n_rows * dvals;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t r = i / dvals;
+    int k = (int)(i % dvals);
+    int count = starts ? starts[r + 1] - starts[r] : 1;
+    float dlt = 0.f, g2 = 0.f;
+    if (count > 0) {
+      float g = ga[r * gastride + k];
+      if (gb) g += gb[r * gbstride + k];
+      g += gamma * (float)count * rows[r * rstride + k];
+      float G = rows[r * rstride + dvals + k];
+      dlt = -lr * g * __frsqrt_rn(G + g * g + eps);
+      g2 = g * g;
+    }
+    out[r * rstride + k] = dlt;
+    out[r * rstride + dvals + k] = g2;
+  }
+}
+
+void adagrad_rows_sum_gpu(const float* ga, const float* gb, const float* rows, float* out,
+                          const int* starts, int64_t n_rows, int dvals, int gastride,
+                          int gbstride, int rstride, float lr, float eps, float gamma,
+                          void* stream) {
+  int64_t total = n_rows * dvals;
+  if (total < 1) return;
+  int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_adagrad_rows_sum, dim3(blocks), dim3(256), 0, (hipStream_t)stream, ga, gb,
+                     rows, out, starts, n_rows, dvals, gastride, gbstride, rstride, lr, eps,
+                     gamma);
+}
+
 }  // namespace adapm

@@ -508,7 +508,9 @@ class Rescal(StepModel):
     psi = e_s^T R e_o with a D x D matrix per relation. Exercises the
     store's NON-UNIFORM value lengths: entity rows 2*D floats, relation
     rows 2*D*D floats, so it pulls and pushes role by role instead of
-    taking the skeleton's one-buffer classic step."""
+    taking the skeleton's one-buffer classic step. The two-sided
+    objective of ComplExConfig (neg_samples_subject, gamma_entity,
+    gamma_relation) selects rescal_step_sides / rescal_step_sides_grouped."""
 
     @staticmethod
     def value_lengths(num_entities, num_relations, dim):
@@ -561,7 +563,7 @@ class Rescal(StepModel):
                               return_ranks)
 
     def train_batch(self, triples: np.ndarray, sync_loss: bool = True,
-                    grouped: bool = None):
+                    grouped: bool = None, neg_keys: np.ndarray = None):
         """One RESCAL step. grouped=True (default on GPU): sort the batch
         by relation, pull each distinct relation matrix ONCE and run the
         three dim^2 products as MFMA-tiled grouped GEMMs
@@ -571,20 +573,31 @@ class Rescal(StepModel):
         B x 2D^2 to G x 2D^2. AdaGrad on dR uses the group-summed
         gradient (minibatch semantics); the classic path transforms each
         triple's outer product separately (both from the same pulled
-        accumulator snapshot)."""
+        accumulator snapshot).
+
+        With cfg.sides (neg_samples_subject, gamma_entity or
+        gamma_relation off its default) the step is the two-sided one,
+        _train_batch_sides. neg_keys names the negatives, sample by
+        sample in the order of `triples` as given."""
         cfg = self.cfg
         w = self.worker
         B = len(triples)
         D = cfg.dim
         if grouped is None:
             grouped = self.dev.type == "cuda" and D % 4 == 0
+        order = None
         if grouped:
             order = np.argsort(triples[:, 1], kind="stable")
             triples = triples[order]
         s_keys = triples[:, 0].astype(np.int64)
         r_keys = (cfg.num_entities + triples[:, 1]).astype(np.int64)
         o_keys = triples[:, 2].astype(np.int64)
-        neg_keys = self._negatives(B * cfg.neg_samples, cfg.num_entities)
+        if cfg.sides:
+            return self._train_batch_sides(s_keys, r_keys, o_keys, order, neg_keys, sync_loss)
+        if neg_keys is None:
+            neg_keys = self._negatives(B * cfg.neg_samples, cfg.num_entities)
+        else:
+            neg_keys = self._by_sample(neg_keys, B, cfg.neg_samples, order)
         opts = dict(dtype=torch.float32, device=self.dev)
         s_v = torch.empty(B, 2 * D, **opts)
         o_v = torch.empty(B, 2 * D, **opts)
@@ -613,4 +626,57 @@ class Rescal(StepModel):
             push_sets = ((s_keys, ds), (r_keys, drl), (o_keys, do), (neg_keys, dn))
         for kt, dt in push_sets:
             self._track(w.push(kt, dt, async_=True))
+        return self._loss_out(loss, sync_loss)
+
+    @staticmethod
+    def _by_sample(keys, B, n, order):
+        """[B*n] keys named sample by sample, in the order the step runs
+        its samples (`order`: the grouped step's sort, else None)."""
+        keys = np.ascontiguousarray(keys, dtype=np.int64).reshape(B, n)
+        return keys.reshape(-1) if order is None else keys[order].reshape(-1)
+
+    def _train_batch_sides(self, s_keys, r_keys, o_keys, order, neg_keys, sync_loss):
+        """The two-sided step (reference train(), knowledge_graph_embeddings.cc:
+        437-531, which RESCAL shares with ComplEx): one draw of
+        B * (neg_samples + neg_samples_subject) keys, the first
+        B * neg_samples corrupt the object and the rest the subject; a fifth
+        pull and push for the subject-side negatives; gamma * E on the
+        positive's rows inside the kernels (rescal_step_sides, and
+        rescal_step_sides_grouped when `order` is the grouped sort)."""
+        cfg = self.cfg
+        w = self.worker
+        B, D, N, NS = len(s_keys), cfg.dim, cfg.neg_samples, cfg.neg_samples_subject
+        if neg_keys is None:
+            neg_keys = self._negatives(B * (N + NS), cfg.num_entities)
+            no_keys, ns_keys = neg_keys[:B * N], neg_keys[B * N:]
+        else:
+            neg_keys = np.asarray(neg_keys, dtype=np.int64)
+            no_keys = self._by_sample(neg_keys[:B * N], B, N, order)
+            ns_keys = self._by_sample(neg_keys[B * N:], B, NS, order)
+        opts = dict(dtype=torch.float32, device=self.dev)
+        s_v = torch.empty(B, 2 * D, **opts)
+        o_v = torch.empty(B, 2 * D, **opts)
+        no_v = torch.empty(B * N, 2 * D, **opts)
+        ns_v = torch.empty(B * NS, 2 * D, **opts)
+        tail = (N, NS, D, cfg.lr, cfg.eps, cfg.gamma_entity, cfg.gamma_relation)
+        if order is not None:
+            rk, starts_np = np.unique(r_keys, return_index=True)
+            starts = np.append(starts_np, B).astype(np.int32)
+        else:
+            rk = r_keys
+        r_v = torch.empty(len(rk), 2 * D * D, **opts)
+        pulls = ((s_keys, s_v), (rk, r_v), (o_keys, o_v), (no_keys, no_v), (ns_keys, ns_v))
+        for kt, vt in pulls:
+            if len(kt):  # a side without negatives has nothing to pull or push
+                w.wait(w.pull(kt, vt, async_=True))
+        deltas = [torch.empty_like(vt) for _, vt in pulls]
+        if order is not None:
+            loss = _C.rescal_step_sides_grouped(s_v, r_v, o_v, no_v, ns_v, *deltas,
+                                                torch.from_numpy(starts), *tail)
+        else:
+            loss = torch.empty(B, dtype=torch.float32, device=self.dev)
+            _C.rescal_step_sides(s_v, r_v, o_v, no_v, ns_v, *deltas, loss, *tail)
+        for (kt, _), dt in zip(pulls, deltas):
+            if len(kt):
+                self._track(w.push(kt, dt, async_=True))
         return self._loss_out(loss, sync_loss)

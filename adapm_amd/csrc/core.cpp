@@ -395,6 +395,16 @@ class UniformStream {
   bool have_owner_ = false;
 };
 
+// What Server::ctr_lookup_fused hands to Server::ctr_update_fused across the
+// dense tower. Python sees an opaque object: the device keys in it were
+// range-checked on the host before their upload and cannot be replaced.
+struct CtrBatch {
+  const void* owner = nullptr;  // the server that staged the keys
+  int64_t n = 0, dim = 0;
+  torch::Tensor sorted, perm;   // device int64 [n]: keys ascending, their occurrences
+  bool used = false;
+};
+
 // ---------------------------------------------------------------- server
 
 class Server {
@@ -3415,6 +3425,77 @@ class Server {
     return loss;
   }
 
+  // Fused CTR embedding step, the two halves around the dense tower
+  // (kernels.h: ctr_gather_fused_gpu, ctr_update_fused_gpu). The update
+  // writes rows with plain stores and takes no row tags: every distinct key
+  // is written by one lane group. That needs what fused_plain_ok spells out,
+  //   (a) a server set up for a single worker thread, checked here, and
+  //   (b) every slab writer enqueued on the caller's current stream, which
+  //       is the caller's side of the contract (backward of an autograd
+  //       Function runs on the stream of its forward),
+  // but not fused_plain_ok itself, whose row tags (one word per key) this
+  // path never reads.
+  void check_ctr_fused(const char* name, int64_t dim) {
+    TORCH_CHECK(dim >= 1 && dim <= CTR_MAX_DIM, name, ": dim = ", dim,
+                " is outside the CTR kernels' range of 1..", CTR_MAX_DIM);
+    check_fused_identity(name, dim);
+    TORCH_CHECK(clocks_.size() == 1, name,
+                " stores without atomics and needs a server with one worker thread");
+  }
+
+  // x[i] = embedding of keys[i] (host int64), and the batch that
+  // ctr_update_fused takes: the device keys, staged and range-checked here,
+  // sorted with the permutation that sorted them.
+  std::tuple<torch::Tensor, std::shared_ptr<CtrBatch>> ctr_lookup_fused(torch::Tensor keys,
+                                                                        int64_t dim) {
+    check_ctr_fused("ctr_lookup_fused", dim);
+    const int64_t n = keys.numel();
+    TORCH_CHECK(n < (int64_t)1 << 31, "ctr_lookup_fused: too many keys in one step");
+    auto batch = std::make_shared<CtrBatch>();
+    batch->owner = this;
+    batch->n = n;
+    batch->dim = dim;
+    auto x = torch::empty({n, dim}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    if (n == 0) return {x, batch};
+    auto sk = stage_keys("ctr_lookup_fused", {&keys});
+    {
+      InflightGuard g(this);
+      ctr_gather_fused_gpu(slab_.data, sk.ptr[0], x.data_ptr<float>(), n, (int)dim,
+                           Slab::padded(uniform_len_), world_, current_stream(dev_));
+    }
+    std::tie(batch->sorted, batch->perm) = torch::sort(sk.dev, /*stable=*/true, 0, false);
+    return {x, batch};
+  }
+
+  void ctr_update_fused(std::shared_ptr<CtrBatch> batch, torch::Tensor grad, int64_t dim,
+                        double lr, double eps) {
+    TORCH_CHECK(batch && batch->owner == this, "ctr_update_fused: batch of another server");
+    TORCH_CHECK(!batch->used, "ctr_update_fused: batch already applied");
+    TORCH_CHECK(batch->dim == dim, "ctr_update_fused: batch was looked up with dim ", batch->dim);
+    const int64_t n = batch->n;
+    TORCH_CHECK(grad.scalar_type() == torch::kFloat32, "ctr_update_fused: grad must be float32");
+    TORCH_CHECK(grad.dim() == 2 && grad.size(0) == n && grad.size(1) == dim,
+                "ctr_update_fused: grad must be [", n, ", ", dim, "]");
+    TORCH_CHECK(grad.is_contiguous(), "ctr_update_fused: grad must be contiguous");
+    TORCH_CHECK(grad.device() == dev_, "ctr_update_fused: grad is not on the store's device");
+    // again: the layout may have broken since the lookup
+    check_ctr_fused("ctr_update_fused", dim);
+    batch->used = true;
+    if (n == 0) return;
+    const int64_t chunks = (n + CTR_SEG_CHUNK - 1) / CTR_SEG_CHUNK;
+    auto scratch = torch::empty({chunks * 2 * dim},
+                                torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    {
+      InflightGuard g(this);
+      ctr_update_fused_gpu(slab_.data, batch->sorted.data_ptr<int64_t>(),
+                           batch->perm.data_ptr<int64_t>(), grad.data_ptr<float>(),
+                           scratch.data_ptr<float>(), n, (int)dim, Slab::padded(uniform_len_),
+                           world_, (float)lr, (float)eps, current_stream(dev_));
+    }
+    count_fused_ops(n);
+    stat_ctr_fused_ += 1;
+  }
+
 
   // --------------------------------------------- spill-tier rebalance
 
@@ -3709,6 +3790,7 @@ class Server {
     // shared rows and so stayed on atomics
     d["fused_plain_steps"] = stat_fused_plain_.load();
     d["fused_atomic_steps"] = stat_fused_atomic_.load();
+    d["ctr_fused_steps"] = stat_ctr_fused_.load();
     {
       std::lock_guard<std::mutex> g(fused_mu_);
       if (fused_shared_stat_.defined())
@@ -3898,6 +3980,7 @@ class Server {
   void* fused_tags_stream_ = nullptr;
   bool fused_multi_stream_ = false;
   std::atomic<int64_t> stat_fused_plain_{0}, stat_fused_atomic_{0};
+  std::atomic<int64_t> stat_ctr_fused_{0};  // ctr_update_fused calls that ran
 };
 
 // ------------------------------------------------------- app kernel wrappers
@@ -4588,6 +4671,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("lo", &UniformStream::lo)
       .def("hi", &UniformStream::hi);
+  m.attr("CTR_SEG_CHUNK") = (int)CTR_SEG_CHUNK;
+  m.attr("CTR_MAX_DIM") = (int)CTR_MAX_DIM;
+  py::class_<CtrBatch, std::shared_ptr<CtrBatch>>(m, "CtrBatch")
+      .def("__len__", [](const CtrBatch& b) { return b.n; });
   py::class_<Server>(m, "Server")
       .def(py::init<int64_t, torch::Tensor, int, int, int, int, std::string, double, int, bool,
                     int64_t, int64_t, double>(),
@@ -4626,6 +4713,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("w2v_step_fused", &Server::w2v_step_fused, py::call_guard<py::gil_scoped_release>())
       .def("mf_step_fused", &Server::mf_step_fused, py::call_guard<py::gil_scoped_release>())
+      .def("ctr_lookup_fused", &Server::ctr_lookup_fused, py::arg("keys"), py::arg("dim"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("ctr_update_fused", &Server::ctr_update_fused, py::arg("batch"), py::arg("grad"),
+           py::arg("dim"), py::arg("lr"), py::arg("eps"),
+           py::call_guard<py::gil_scoped_release>())
       .def("kge_step_fused_general", &Server::kge_step_fused_general,
            py::call_guard<py::gil_scoped_release>())
       .def("kge_step_sides_fused", &Server::kge_step_sides_fused,

@@ -20,6 +20,18 @@ namespace adapm {
 // the CPU twins have no such limit.
 constexpr int STEP_MAX_LANES = 8 * 256;
 
+// The fused CTR kernels (ctr_hip.hip) give a row's floats to the lanes of a
+// lane group, 4 floats per lane where D % 4 == 0 and the pointers are 16-byte
+// aligned, else 1. A group is at most one wave (64 lanes) and holds one
+// column block of a row at a time; longer rows take further passes over the
+// same keys. The limit below is 16 passes of the one-float mapping, 4 of the
+// four-float one; the bindings refuse a longer row before enqueueing.
+constexpr int CTR_MAX_DIM = 1024;
+
+// Positions of the sorted key array that one lane group of ctr_update_fused
+// sums serially (a "chunk").
+constexpr int CTR_SEG_CHUNK = 32;
+
 // ComplEx training step over B positives with N o-side negatives each.
 //  s, r, o:   [B][2D]   pulled rows (emb | accum)
 //  neg:       [B*N][2D] pulled negative-entity rows
@@ -174,6 +186,57 @@ void w2v_sgns_step_fused_gpu(float* slab, const int64_t* keys_ctr, const int64_t
 void mf_update_step_fused_gpu(float* slab, const int64_t* keys_w, const int64_t* keys_h,
                               const float* x, float* loss, int B, int R, int32_t plen,
                               int world, float lr, float lambda, float eps, void* stream);
+
+// FUSED CTR embedding step (identity layout only: key k at (k/world)*plen),
+// the two halves of a wide-and-deep step on either side of the dense tower.
+//
+// ctr_gather_fused_gpu: x[i][0:D] = emb half of the row of keys[i], for the
+// n key occurrences of a batch in the caller's order. No unique, no
+// accumulator half, no intermediate buffer.
+//
+// ctr_update_fused_gpu: for every distinct key u of the batch
+//   g = sum of grad[i] over the occurrences i of u
+//   emb += -lr * g / sqrt(acc + g*g + eps),  acc += g*g
+// written into the row in place: ONE AdaGrad update of the complete sum per
+// key, as the classic step does after its unique + scatter-add. Inputs:
+//   keys_sorted [n]  the batch's keys, ascending (device)
+//   perm [n]         occurrence of each sorted position: keys_sorted[p] is
+//                    the key of occurrence perm[p], grad row perm[p]
+//   grad [n][D]      gradient of x
+//   scratch          2 * D * ceil(n / CTR_SEG_CHUNK) floats, contents irrelevant
+// How the work is split: the sorted array is cut into chunks of CTR_SEG_CHUNK
+// positions and every chunk goes to one lane group (the row's column block
+// spread over 1..64 lanes, so a wave carries 64 / lanes chunks), whatever the
+// key distribution. A group walks its chunk with the sum of the current run
+// of equal keys in registers. Everything it needs to know about a run it
+// reads from keys_sorted: a run begins inside the chunk if the position
+// before it holds another key (or is the array's start) and ends inside if
+// the position after it does (or is the array's end).
+//   - a run that begins and ends inside is a whole segment: the group reads
+//     the row, applies AdaGrad and stores both halves;
+//   - a run open on the left (whether or not it is open on the right too)
+//     stores its sum to scratch[chunk][0], one open only on the right to
+//     scratch[chunk][1].
+// A second launch gives one wave to every chunk whose slot 1 is in use (the
+// HEAD of a segment that spans chunks; exactly one per such segment, since
+// every later chunk of the segment sees it open on the left). The wave finds
+// the segment's end by binary search in keys_sorted, so it knows the chunks
+// whose slot 0 belongs to the segment; its groups add them in a fixed strided
+// order, a butterfly over the groups joins their sums, and group 0 does the
+// AdaGrad write. A group serially adds at most CTR_SEG_CHUNK gradient rows,
+// or the partials of one segment.
+// Every slab write is a plain store and no launch holds an atomic: each
+// distinct key is written by exactly one group. The order of all additions
+// is fixed by (n, D, keys), so two runs from one state agree bit for bit.
+// The caller guarantees what plain stores need: nothing else writes the slab
+// while the launches run, i.e. the server has a single worker thread and
+// every slab writer is enqueued on `stream`. 1 <= D <= CTR_MAX_DIM; n == 0
+// is a no-op.
+void ctr_gather_fused_gpu(const float* slab, const int64_t* keys, float* x, int64_t n, int D,
+                          int32_t plen, int world, void* stream);
+void ctr_update_fused_gpu(float* slab, const int64_t* keys_sorted, const int64_t* perm,
+                          const float* grad, float* scratch, int64_t n, int D, int32_t plen,
+                          int world, float lr, float eps, void* stream);
 
 // ComplEx scoring only (evaluation): score[b][e] = psi(s_b, r_b, cand_e)
 //  cand: [E][2D] candidate entity rows; scores: [B][E]

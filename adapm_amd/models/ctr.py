@@ -99,6 +99,56 @@ class WideAndDeep(StepModel):
         self._track(w.push(keys_u, delta, async_=True))
         return self._loss_out(loss, sync_loss)
 
+    def _ctr_fused_ok(self):
+        """The fused CTR step stores without atomics: identity layout on one
+        GPU rank, and a server set up for a single worker thread."""
+        return (self._fused_identity(False)
+                and len(self.server.raw.worker_clocks()) == 1)
+
+    def train_batch_fused(self, feats: np.ndarray, labels: np.ndarray, sync_loss=True):
+        """train_batch with the embedding path on the slab itself: one gather
+        of the B * fields occurrences straight from the store, the same
+        tower, loss and dense optimizer step, and in backward one segmented
+        AdaGrad write-back (FusedEmbedding). The same update per distinct key
+        as train_batch: one AdaGrad step of the key's summed gradient. Where
+        the fused path cannot run, this is train_batch."""
+        if not self._ctr_fused_ok():
+            return self.train_batch(feats, labels, sync_loss)
+        cfg = self.cfg
+        B, F = feats.shape
+        keys = torch.from_numpy(np.ascontiguousarray(feats.reshape(-1), dtype=np.int64))
+        x = FusedEmbedding.lookup(self.server.raw, keys, cfg.dim, cfg.lr, cfg.eps)
+        logits = self.net(x.view(B, F * cfg.dim)).squeeze(1)
+        y = torch.as_tensor(labels.astype(np.float32), device=self.dev)
+        loss = torch.nn.functional.binary_cross_entropy_with_logits(logits, y)
+        self.opt.zero_grad(set_to_none=True)
+        loss.backward()
+        self.opt.step()
+        return self._loss_out(loss, sync_loss)
+
+
+class FusedEmbedding(torch.autograd.Function):
+    """x[i] = embedding of keys[i], read from the store's slab; backward
+    applies AdaGrad of each distinct key's summed gradient to the slab in
+    place and hands no gradient to anyone. `raw` is the native server, `keys`
+    a host int64 tensor. `anchor` is any tensor that requires grad: autograd
+    only runs the backward of a Function one of whose inputs does."""
+
+    @staticmethod
+    def forward(ctx, anchor, raw, keys, dim, lr, eps):
+        x, ctx.batch = raw.ctr_lookup_fused(keys, dim)
+        ctx.raw, ctx.args = raw, (dim, lr, eps)
+        return x
+
+    @staticmethod
+    def backward(ctx, grad):
+        ctx.raw.ctr_update_fused(ctx.batch, grad.contiguous(), *ctx.args)
+        return (None,) * 6
+
+    @classmethod
+    def lookup(cls, raw, keys, dim, lr, eps):
+        return cls.apply(torch.zeros(1, requires_grad=True), raw, keys, dim, lr, eps)
+
 
 def make_synthetic_ctr(n, num_features, fields, zipf_a=1.1, seed=0):
     rng = np.random.default_rng(seed)

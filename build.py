@@ -33,8 +33,15 @@ SOURCES = [
     "core.cpp",
     "kernels_hip.hip",
     "mfma_hip.hip",
+    "ctr_hip.hip",
     "kernels_cpu.cpp",
 ]
+
+# Per-source flags. ctr_hip.hip adds float4 lanes element by element; it is
+# built without the packed fp32 instructions.
+EXTRA_FLAGS = {
+    "ctr_hip.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 MODULE = "_C"
 
@@ -75,7 +82,7 @@ def build(verbose: bool = True, tsan: bool = False) -> Path:
         objs.append(op)
         if op.exists() and op.stat().st_mtime > max(sp.stat().st_mtime, hdr_mtime):
             continue
-        cmd = ["hipcc", "-c", str(sp), "-o", str(op)] + cflags
+        cmd = ["hipcc", "-c", str(sp), "-o", str(op)] + cflags + EXTRA_FLAGS.get(src, [])
         jobs.append((src, cmd))
 
     def run(job):

@@ -35,6 +35,9 @@ def main():
                     help=">0: call rebalance_spill every N steps (tiered store "
                          "keeps the hot set HBM-resident; world==1 only)")
     ap.add_argument("--rebalance-moves", type=int, default=131072)
+    ap.add_argument("--fused", action="store_true",
+                    help="train_batch_fused: slab-direct gather and segmented "
+                         "AdaGrad write-back (world==1, identity layout)")
     ap.add_argument("--rebalance-warmup-only", action="store_true",
                     help="stop rebalancing when the timed region starts (isolates "
                          "steady-state layout effect from rebalance call cost)")
@@ -77,9 +80,10 @@ def main():
             rebal_stats["n"] += 1
 
     is_cuda = server.rt.device.type == "cuda"
+    step = model.train_batch_fused if args.fused else model.train_batch
     for i in range(args.warmup):
         maybe_rebalance(i)
-        model.train_batch(*batches[i], sync_loss=False)
+        step(*batches[i], sync_loss=False)
     model.drain()
     worker.barrier()
     if is_cuda:
@@ -90,7 +94,7 @@ def main():
             model.signal_intent(batches[i + 1][0], worker.current_clock() + 1,
                                 worker.current_clock() + 3)
         maybe_rebalance(i)
-        model.train_batch(*batches[i], sync_loss=False)
+        step(*batches[i], sync_loss=False)
         worker.advance_clock()
     model.drain()
     if is_cuda:
@@ -122,6 +126,8 @@ def main():
                        "host_spill_in_use_gb": st["host_spill_in_use"] * 4 / (1 << 30),
                        "spill_rebalance_moves": st.get("spill_rebalance_moves", 0),
                        "hash_ids": args.hash_ids,
+                       "fused": args.fused,
+                       "ctr_fused_steps": st.get("ctr_fused_steps", 0),
                        "pull_push_ops_per_s": 2 * args.batch * args.fields * args.steps * world / el,
                        "parallelism": f"ps-async-dp{world}"},
         }), flush=True)

@@ -3317,6 +3317,95 @@ class Server {
         });
   }
 
+  // Fused RESCAL step (kernels.h, rescal_step_fused_gpu) on the general path;
+  // there is no identity path for a store of two value lengths. The samples
+  // come sorted by relation: keys_r is made of runs, and since compaction
+  // keeps the order so are the relation offsets of the hit samples. The runs
+  // become the groups; starts, offs_rg and the table of 16-row tiles are
+  // built here and go up as ONE blob next to the four offset arrays. All
+  // arguments are checked before the metadata pass touches a key.
+  std::tuple<torch::Tensor, torch::Tensor> rescal_step_fused_general(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, torch::Tensor keys_neg,
+      int64_t N, int64_t D, double lr, double eps) {
+    const char* name = "rescal_step_fused";
+    TORCH_CHECK(N >= 0, name, ": N = ", N, " must be >= 0");
+    TORCH_CHECK(D >= 4 && D % 4 == 0, name, ": D = ", D, " must be a positive multiple of 4");
+    if (dev_.is_cuda())
+      TORCH_CHECK(D <= RESCAL_FUSED_MAX_DIM, name, ": D = ", D, " exceeds the GPU kernels' limit of ",
+                  RESCAL_FUSED_MAX_DIM);
+    const int64_t B = keys_s.numel();
+    TORCH_CHECK(B * std::max<int64_t>(N, 1) < ((int64_t)1 << 31), name,
+                ": too many keys in one step");
+    const torch::Tensor* roles[4] = {&keys_s, &keys_o, &keys_neg, &keys_r};
+    const int64_t want[4] = {B, B, B * N, B};
+    for (int a = 0; a < 4; ++a) {
+      check_keys(*roles[a]);
+      check_key_range(*roles[a]);
+      TORCH_CHECK(roles[a]->numel() == want[a], name, ": key arrays disagree on the batch");
+      const int64_t* kp = roles[a]->data_ptr<int64_t>();
+      const int64_t len = a < 3 ? 2 * D : 2 * D * D;
+      for (int64_t i = 0; i < want[a]; ++i)
+        TORCH_CHECK(len_of(kp[i]) == len, name, ": key ", kp[i], " has a row of ", len_of(kp[i]),
+                    " floats, ", a < 3 ? "an entity" : "a relation", " row has ", len);
+    }
+    {
+      const int64_t* kr = keys_r.data_ptr<int64_t>();
+      std::unordered_set<int64_t> seen;
+      for (int64_t i = 0; i < B; ++i) {
+        if (i && kr[i] == kr[i - 1]) continue;
+        TORCH_CHECK(seen.insert(kr[i]).second, name, ": relation key ", kr[i],
+                    " reappears at position ", i, "; the samples must be sorted by relation");
+      }
+    }
+    return step_fused_general(
+        name, {{&keys_s, 1}, {&keys_r, 1}, {&keys_o, 1}, {&keys_neg, N}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          const std::vector<int64_t>& ro = res.offs[1];
+          std::vector<int64_t> offs_rg;
+          std::vector<int32_t> starts, tiles;
+          for (int b = 0; b < Bh; ++b) {
+            if (b && ro[b] == ro[b - 1]) continue;
+            offs_rg.push_back(ro[b]);
+            starts.push_back(b);
+          }
+          starts.push_back(Bh);
+          const int G = (int)offs_rg.size();
+          if (!dev_.is_cuda()) {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            rescal_step_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3],
+                                       offs_rg.data(), starts.data(), loss, Bh, G, (int)N, (int)D,
+                                       (float)lr, (float)eps);
+            return;
+          }
+          for (auto& o : res.offs)
+            for (int64_t v : o)
+              TORCH_CHECK((v & 3) == 0, name, ": a row does not start on a 16-byte boundary");
+          for (int g = 0; g < G; ++g)
+            for (int m0 = 0; m0 < starts[g + 1] - starts[g]; m0 += 16) {
+              tiles.push_back(g);
+              tiles.push_back(m0);
+            }
+          // blob: offs_rg | starts | tiles, the int32 parts padded to whole words
+          const size_t w_starts = (starts.size() + 1) / 2, w_tiles = tiles.size() / 2;
+          std::vector<int64_t> blob(G + w_starts + w_tiles, 0);
+          std::memcpy(blob.data(), offs_rg.data(), G * sizeof(int64_t));
+          std::memcpy(blob.data() + G, starts.data(), starts.size() * sizeof(int32_t));
+          std::memcpy(blob.data() + G + w_starts, tiles.data(), tiles.size() * sizeof(int32_t));
+          auto blob_d = offs_to_dev(blob);
+          const int64_t* bp = blob_d.data_ptr<int64_t>();
+          auto scratch = torch::empty({3, (int64_t)Bh, D},
+                                      torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+          float* sp = scratch.data_ptr<float>();
+          const int64_t bd = (int64_t)Bh * D;
+          rescal_step_fused_gpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3], bp,
+                                reinterpret_cast<const int32_t*>(bp + G),
+                                reinterpret_cast<const int32_t*>(bp + G + w_starts),
+                                (int)w_tiles, sp, sp + bd, sp + 2 * bd, loss, Bh, G, (int)N,
+                                (int)D, (float)lr, (float)eps, current_stream(dev_));
+        });
+  }
+
   std::tuple<torch::Tensor, torch::Tensor> w2v_step_fused_general(
       torch::Tensor keys_ctr, torch::Tensor keys_ctx, torch::Tensor keys_neg, int64_t N,
       int64_t D, double lr, double eps) {
@@ -4673,6 +4762,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("hi", &UniformStream::hi);
   m.attr("CTR_SEG_CHUNK") = (int)CTR_SEG_CHUNK;
   m.attr("CTR_MAX_DIM") = (int)CTR_MAX_DIM;
+  m.attr("RESCAL_FUSED_MAX_DIM") = (int)RESCAL_FUSED_MAX_DIM;
   py::class_<CtrBatch, std::shared_ptr<CtrBatch>>(m, "CtrBatch")
       .def("__len__", [](const CtrBatch& b) { return b.n; });
   py::class_<Server>(m, "Server")
@@ -4725,6 +4815,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("kge_step_sides_fused_sampled", &Server::kge_step_sides_fused_sampled,
            py::call_guard<py::gil_scoped_release>())
       .def("kge_step_sides_fused_general", &Server::kge_step_sides_fused_general,
+           py::call_guard<py::gil_scoped_release>())
+      .def("rescal_step_fused_general", &Server::rescal_step_fused_general,
            py::call_guard<py::gil_scoped_release>())
       .def("w2v_step_fused_general", &Server::w2v_step_fused_general,
            py::call_guard<py::gil_scoped_release>())

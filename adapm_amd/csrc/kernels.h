@@ -285,6 +285,53 @@ void rescal_step_sides_cpu(const float* s, const float* r, const float* o, const
                            float* dneg_o, float* dneg_s, float* loss, int B, int N, int NS,
                            int D, float lr, float eps, float gamma_e, float gamma_r);
 
+// FUSED RESCAL step (rescal_fused_hip.hip): the one-sided grouped step (N
+// object-side negatives, no regulariser) on the slab's own rows, offsets mode
+// only: every row is slab + offs[i], offs in floats and multiples of 4 (rows
+// start on 16-byte boundaries; the binding checks it). Entity rows are
+// [emb(D) | acc(D)], relation rows [R(D*D) | acc(D*D)], R row-major.
+//   offs_s, offs_o [B], offs_neg [B*N]   the triples, SORTED BY RELATION
+//   offs_rg [G], starts [G+1]            group g = triples [starts[g],
+//                                        starts[g+1]), all of relation offs_rg[g];
+//                                        no group is empty
+//   tiles [n_tiles][2]                   (g, m0) for every 16-row tile of every
+//                                        group, m0 counted within the group
+//   U, W, Sc [B][D]                      scratch, contents irrelevant
+//   loss [B]                             in the sorted order
+// Four launches on `stream`:
+//   1  U = S_g R_g (u_b = R^T s_b), s gathered from the slab; Sc[b] = s_b
+//   2  per triple: psi_j = u . o_j, c_j = -y_j / (1 + exp(y_j psi_j)),
+//      W[b] = sum_j c_j o_j; o and every o'_j get their AdaGrad update of
+//      c_j u in place; loss[b]
+//   3  s_b += AdaGrad(R_g W[b])           from the accumulators, no ds buffer
+//   4  R_g += AdaGrad(sum_b Sc[b] W[b]^T) the group-summed gradient, as
+//      rescal_step_grouped
+// Launch 3 reads the R that launch 4 writes, and launch 4 reads Sc, not the s
+// that launch 3 has moved: on a batch of distinct keys the result is the
+// grouped step's. Every slab write is an atomicAdd of the delta and of g^2,
+// the accumulator read before it a plain load, as slab_adagrad(shared = true):
+// a key named more than once in a batch sees hogwild-style concurrent updates
+// (async-PS semantics), and an entity that is an o or o' and also an s has had
+// its accumulator moved by launch 2 when launch 3 reads it. That is the
+// contract of every fused step here.
+// D % 4 == 0, 4 <= D <= RESCAL_FUSED_MAX_DIM; callers check. B, G or n_tiles
+// < 1 is a no-op. adagrad_delta and the softplus are repeated in the .hip
+// file rather than shared with kernels_hip.hip, whose KPT = 8 kernels have a
+// register allocation that moving code around has broken before.
+// The CPU twin is serial and in place: per triple it takes a copy of s, runs
+// launch 2's loop on the rows themselves, then updates s; R is updated at the
+// end of its group.
+constexpr int RESCAL_FUSED_MAX_DIM = 256;
+void rescal_step_fused_gpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                           const int64_t* offs_neg, const int64_t* offs_rg, const int32_t* starts,
+                           const int32_t* tiles, int n_tiles, float* U, float* W, float* Sc,
+                           float* loss, int B, int G, int N, int D, float lr, float eps,
+                           void* stream);
+void rescal_step_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                const int64_t* offs_neg, const int64_t* offs_rg,
+                                const int32_t* starts, float* loss, int B, int G, int N, int D,
+                                float lr, float eps);
+
 // word2vec SGNS step: per center/context pair with N negatives.
 //  ctr:  [B][2D] center (syn0) rows;  ctx: [B][2D] context (syn1) rows
 //  neg:  [B*N][2D] negative (syn1) rows

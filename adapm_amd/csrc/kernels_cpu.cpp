@@ -443,6 +443,55 @@ void mf_update_step_fused_offs_cpu(float* slab, const int64_t* offs_w, const int
   }
 }
 
+// Fused RESCAL step in place (kernels.h): triples sorted by relation, R_g
+// read as it was for the whole group and updated once, from the group-summed
+// gradient, when the group is done.
+void rescal_step_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                const int64_t* offs_neg, const int64_t* offs_rg,
+                                const int32_t* starts, float* loss, int B, int G, int N, int D,
+                                float lr, float eps) {
+  const int64_t dd = (int64_t)D * D;
+  std::vector<float> sv(D), u(D), w(D);
+  std::vector<double> dR(dd);
+  for (int g = 0; g < G; ++g) {
+    float* R = slab + offs_rg[g];
+    std::fill(dR.begin(), dR.end(), 0.0);
+    for (int b = starts[g]; b < starts[g + 1] && b < B; ++b) {
+      float* sb = slab + offs_s[b];
+      std::copy(sb, sb + D, sv.begin());
+      for (int j = 0; j < D; ++j) {  // u = R^T s
+        double a = 0;
+        for (int i = 0; i < D; ++i) a += R[(int64_t)i * D + j] * sv[i];
+        u[j] = (float)a;
+      }
+      std::fill(w.begin(), w.end(), 0.f);
+      float lsum = 0.f;
+      for (int j = 0; j <= N; ++j) {
+        float* ob = slab + ((j == 0) ? offs_o[b] : offs_neg[(int64_t)b * N + (j - 1)]);
+        float y = (j == 0) ? 1.f : -1.f;
+        double dot = 0;
+        for (int k = 0; k < D; ++k) dot += u[k] * ob[k];
+        float c = -y * sigmoidf_(-y * (float)dot);
+        lsum += softplusf_(-y * (float)dot);
+        for (int k = 0; k < D; ++k) {
+          w[k] += c * ob[k];
+          adagrad_inplace(ob[k], ob[D + k], c * u[k], lr, eps);
+        }
+      }
+      loss[b] = lsum;
+      for (int i = 0; i < D; ++i) {  // ds = R w, dR += s w^T
+        double a = 0;
+        for (int k = 0; k < D; ++k) {
+          a += R[(int64_t)i * D + k] * w[k];
+          dR[(int64_t)i * D + k] += (double)sv[i] * w[k];
+        }
+        adagrad_inplace(sb[i], sb[D + i], (float)a, lr, eps);
+      }
+    }
+    for (int64_t i = 0; i < dd; ++i) adagrad_inplace(R[i], R[dd + i], (float)dR[i], lr, eps);
+  }
+}
+
 void mf_loss_cpu(const float* w, const float* h, const float* x, float* out2, int B, int R,
                  float lambda) {
   const int row = R << 1;

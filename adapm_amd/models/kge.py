@@ -510,7 +510,9 @@ class Rescal(StepModel):
     rows 2*D*D floats, so it pulls and pushes role by role instead of
     taking the skeleton's one-buffer classic step. The two-sided
     objective of ComplExConfig (neg_samples_subject, gamma_entity,
-    gamma_relation) selects rescal_step_sides / rescal_step_sides_grouped."""
+    gamma_relation) selects rescal_step_sides / rescal_step_sides_grouped.
+    train_batch_fused is the opt-in slab-direct step of the one-sided
+    objective."""
 
     @staticmethod
     def value_lengths(num_entities, num_relations, dim):
@@ -627,6 +629,51 @@ class Rescal(StepModel):
         for kt, dt in push_sets:
             self._track(w.push(kt, dt, async_=True))
         return self._loss_out(loss, sync_loss)
+
+    # ----------------------------------------------------- fused step
+
+    def train_batch_fused(self, triples: np.ndarray, sync_loss: bool = False,
+                          force_general: bool = False, neg_keys: np.ndarray = None):
+        """Fused slab-direct step (Server.rescal_step_fused_general): the
+        kernels gather s from the slab, update o and the negatives where
+        they score them and write the AdaGrad updates of s and R from
+        the MFMA accumulators; no pulled or delta buffer. One-sided
+        objective only: with cfg.sides, off the GPU (unless
+        force_general, which runs the general path on a CPU store), and
+        for a dim the kernels do not take, this is train_batch. Samples
+        with a key that is not local go through train_batch as well,
+        deferred by one step first (StepModel._fused_step). neg_keys as
+        in train_batch."""
+        cfg = self.cfg
+        if (cfg.sides or (self.dev.type != "cuda" and not force_general)
+                or cfg.dim % 4 or cfg.dim > _C.RESCAL_FUSED_MAX_DIM):
+            return self.train_batch(triples, sync_loss=sync_loss, neg_keys=neg_keys)
+        B = len(triples)
+        if neg_keys is None:
+            neg_keys = self._negatives(B * cfg.neg_samples, cfg.num_entities)
+        negs2 = np.ascontiguousarray(neg_keys, dtype=np.int64).reshape(B, cfg.neg_samples)
+        return self._fused_step((triples, negs2), sync_loss, force_general)
+
+    def _fused_identity(self, force_general):
+        return False  # no identity layout for two value lengths
+
+    def _fused_general_step(self, arrays):
+        """The kernels want the samples in runs of one relation; deferred
+        samples sit in front of the batch, so sort here. `missed` comes
+        back as positions in the sorted order."""
+        cfg = self.cfg
+        triples, negs2 = arrays
+        order = np.argsort(triples[:, 1], kind="stable")
+        t = triples[order]
+        keys = (t[:, 0], cfg.num_entities + t[:, 1], t[:, 2], negs2[order].reshape(-1))
+        loss, missed = self.server.raw.rescal_step_fused_general(
+            *(torch.from_numpy(np.ascontiguousarray(k, dtype=np.int64)) for k in keys),
+            cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
+        return loss, torch.from_numpy(order[missed.numpy()])
+
+    def _classic_step(self, arrays):
+        triples, negs2 = arrays
+        return self.train_batch(triples, sync_loss=False, neg_keys=negs2.reshape(-1))
 
     @staticmethod
     def _by_sample(keys, B, n, order):

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""RESCAL whole-step A/B on a real world-1 GPU store: Rescal.train_batch
+(grouped: four pulls, six launches, four pushes) against
+Rescal.train_batch_fused (host offset pass, four slab-direct launches).
+Unlike scripts/bench_rescal.py, which times the kernels on resident
+buffers, a step here includes everything a training loop pays for, and the
+clock stops only after drain() and a device synchronise.
+
+Both paths run the same batches with the same pre-drawn negatives, in the
+order F C C F, twice, in one process; every run and the medians are printed,
+then one JSON line.
+
+Run on a GPU box:  python scripts/bench_rescal_fused.py [--dim 128] [--batch 2048]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--entities", type=int, default=100_000)
+    ap.add_argument("--relations", type=int, default=32)
+    ap.add_argument("--dim", type=int, default=128)
+    ap.add_argument("--batch", type=int, default=2048)
+    ap.add_argument("--neg", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--order", type=str, default="FCCFFCCF",
+                    help="the runs, F fused and C classic; a profile wants one path, e.g. F")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "this benchmark measures the GPU store"
+
+    import adapm_amd
+    from adapm_amd.models.kge import ComplExConfig, Rescal
+
+    E, R, D, B, N = args.entities, args.relations, args.dim, args.batch, args.neg
+    cfg = ComplExConfig(num_entities=E, num_relations=R, dim=D, neg_samples=N, batch_size=B)
+    adapm_amd.setup(num_keys=E + R, num_threads=1, device="cuda:0")
+    server = adapm_amd.Server(torch.from_numpy(Rescal.value_lengths(E, R, D)))
+    worker = adapm_amd.Worker(0, server)
+    model = Rescal(cfg, server, worker)
+    model.init_embeddings()
+
+    rng = np.random.default_rng(0)
+    total = args.warmup + args.steps
+    batches = [(np.stack([rng.integers(0, E, B), rng.integers(0, R, B), rng.integers(0, E, B)],
+                         axis=1).astype(np.int64),
+                rng.integers(0, E, B * N, dtype=np.int64)) for _ in range(total)]
+
+    def classic(t, neg):
+        model.train_batch(t, sync_loss=False, grouped=True, neg_keys=neg)
+
+    def fused(t, neg):
+        model.train_batch_fused(t, sync_loss=False, neg_keys=neg)
+
+    def run(step):
+        for t, neg in batches[:args.warmup]:
+            step(t, neg)
+        model.drain()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for t, neg in batches[args.warmup:]:
+            step(t, neg)
+        model.drain()
+        torch.cuda.synchronize()
+        return 1000 * (time.perf_counter() - t0) / args.steps
+
+    ms = {"fused": [], "classic": []}
+    for name in ("fused" if c == "F" else "classic" for c in args.order.upper()):
+        ms[name].append(run(fused if name == "fused" else classic))
+        print(f"{name}: {ms[name][-1]:.3f} ms/step", flush=True)
+    med = {k: statistics.median(v) if v else float("nan") for k, v in ms.items()}
+    print(f"median: classic {med['classic']:.3f} ms, fused {med['fused']:.3f} ms, "
+          f"classic / fused = {med['classic'] / med['fused']:.2f}x "
+          f"(E={E}, R={R}, D={D}, B={B}, N={N})")
+    print(json.dumps({"metric": "rescal_step_ms", "classic_ms": ms["classic"],
+                      "fused_ms": ms["fused"], "classic_median_ms": med["classic"],
+                      "fused_median_ms": med["fused"],
+                      "ratio": med["classic"] / med["fused"],
+                      "config": {"entities": E, "relations": R, "dim": D, "batch": B, "neg": N,
+                                 "steps": args.steps, "warmup": args.warmup}}), flush=True)
+    worker.finalize()
+    server.shutdown()
+
+
+if __name__ == "__main__":
+    main()

@@ -3329,81 +3329,169 @@ class Server {
       int64_t N, int64_t D, double lr, double eps) {
     const char* name = "rescal_step_fused";
     TORCH_CHECK(N >= 0, name, ": N = ", N, " must be >= 0");
-    TORCH_CHECK(D >= 4 && D % 4 == 0, name, ": D = ", D, " must be a positive multiple of 4");
-    if (dev_.is_cuda())
-      TORCH_CHECK(D <= RESCAL_FUSED_MAX_DIM, name, ": D = ", D, " exceeds the GPU kernels' limit of ",
-                  RESCAL_FUSED_MAX_DIM);
-    const int64_t B = keys_s.numel();
-    TORCH_CHECK(B * std::max<int64_t>(N, 1) < ((int64_t)1 << 31), name,
-                ": too many keys in one step");
-    const torch::Tensor* roles[4] = {&keys_s, &keys_o, &keys_neg, &keys_r};
-    const int64_t want[4] = {B, B, B * N, B};
-    for (int a = 0; a < 4; ++a) {
-      check_keys(*roles[a]);
-      check_key_range(*roles[a]);
-      TORCH_CHECK(roles[a]->numel() == want[a], name, ": key arrays disagree on the batch");
-      const int64_t* kp = roles[a]->data_ptr<int64_t>();
-      const int64_t len = a < 3 ? 2 * D : 2 * D * D;
-      for (int64_t i = 0; i < want[a]; ++i)
-        TORCH_CHECK(len_of(kp[i]) == len, name, ": key ", kp[i], " has a row of ", len_of(kp[i]),
-                    " floats, ", a < 3 ? "an entity" : "a relation", " row has ", len);
-    }
-    {
-      const int64_t* kr = keys_r.data_ptr<int64_t>();
-      std::unordered_set<int64_t> seen;
-      for (int64_t i = 0; i < B; ++i) {
-        if (i && kr[i] == kr[i - 1]) continue;
-        TORCH_CHECK(seen.insert(kr[i]).second, name, ": relation key ", kr[i],
-                    " reappears at position ", i, "; the samples must be sorted by relation");
-      }
-    }
+    check_rescal_fused(name, {{&keys_s, 1, nullptr}, {&keys_o, 1, nullptr}, {&keys_neg, N, nullptr}},
+                       keys_r, D);
     return step_fused_general(
         name, {{&keys_s, 1}, {&keys_r, 1}, {&keys_o, 1}, {&keys_neg, N}},
         [&](const FusedResolve& res, float* loss) {
           const int Bh = (int)res.b_hit;
-          const std::vector<int64_t>& ro = res.offs[1];
-          std::vector<int64_t> offs_rg;
-          std::vector<int32_t> starts, tiles;
-          for (int b = 0; b < Bh; ++b) {
-            if (b && ro[b] == ro[b - 1]) continue;
-            offs_rg.push_back(ro[b]);
-            starts.push_back(b);
-          }
-          starts.push_back(Bh);
-          const int G = (int)offs_rg.size();
+          const RescalGroups gr = rescal_groups(res.offs[1], Bh);
           if (!dev_.is_cuda()) {
             std::lock_guard<std::mutex> vg(cpu_val_mu_);
             rescal_step_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3],
-                                       offs_rg.data(), starts.data(), loss, Bh, G, (int)N, (int)D,
-                                       (float)lr, (float)eps);
+                                       gr.offs_rg.data(), gr.starts.data(), loss, Bh, gr.G, (int)N,
+                                       (int)D, (float)lr, (float)eps);
             return;
           }
-          for (auto& o : res.offs)
-            for (int64_t v : o)
-              TORCH_CHECK((v & 3) == 0, name, ": a row does not start on a 16-byte boundary");
-          for (int g = 0; g < G; ++g)
-            for (int m0 = 0; m0 < starts[g + 1] - starts[g]; m0 += 16) {
-              tiles.push_back(g);
-              tiles.push_back(m0);
-            }
-          // blob: offs_rg | starts | tiles, the int32 parts padded to whole words
-          const size_t w_starts = (starts.size() + 1) / 2, w_tiles = tiles.size() / 2;
-          std::vector<int64_t> blob(G + w_starts + w_tiles, 0);
-          std::memcpy(blob.data(), offs_rg.data(), G * sizeof(int64_t));
-          std::memcpy(blob.data() + G, starts.data(), starts.size() * sizeof(int32_t));
-          std::memcpy(blob.data() + G + w_starts, tiles.data(), tiles.size() * sizeof(int32_t));
-          auto blob_d = offs_to_dev(blob);
-          const int64_t* bp = blob_d.data_ptr<int64_t>();
+          const RescalBlob bl = rescal_blob(name, res, gr);
           auto scratch = torch::empty({3, (int64_t)Bh, D},
                                       torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
           float* sp = scratch.data_ptr<float>();
           const int64_t bd = (int64_t)Bh * D;
-          rescal_step_fused_gpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3], bp,
-                                reinterpret_cast<const int32_t*>(bp + G),
-                                reinterpret_cast<const int32_t*>(bp + G + w_starts),
-                                (int)w_tiles, sp, sp + bd, sp + 2 * bd, loss, Bh, G, (int)N,
-                                (int)D, (float)lr, (float)eps, current_stream(dev_));
+          rescal_step_fused_gpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3], bl.offs_rg,
+                                bl.starts, bl.tiles, bl.n_tiles, sp, sp + bd, sp + 2 * bd, loss, Bh,
+                                gr.G, (int)N, (int)D, (float)lr, (float)eps, current_stream(dev_));
         });
+  }
+
+  // The two-sided fused RESCAL step (kernels.h, rescal_step_sides_fused_gpu):
+  // the entry above with a fifth key role, the subject-side negatives, and one
+  // scratch tensor for U, V, W, Z, Sc, Oc and c0. With NS = 0 and both gammas
+  // 0 it IS the entry above, so that the case is bit-equal by construction.
+  std::tuple<torch::Tensor, torch::Tensor> rescal_step_sides_fused_general(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, torch::Tensor keys_neg_o,
+      torch::Tensor keys_neg_s, int64_t N, int64_t NS, int64_t D, double lr, double eps,
+      double gamma_e, double gamma_r) {
+    const char* name = "rescal_step_sides_fused";
+    TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+    TORCH_CHECK(std::isfinite(gamma_e) && gamma_e >= 0 && std::isfinite(gamma_r) && gamma_r >= 0,
+                name, ": gamma_e = ", gamma_e, " and gamma_r = ", gamma_r,
+                " must be finite and >= 0");
+    check_rescal_fused(name,
+                       {{&keys_s, 1, "keys_s"}, {&keys_o, 1, "keys_o"}, {&keys_neg_o, N, "keys_neg_o"},
+                        {&keys_neg_s, NS, "keys_neg_s"}},
+                       keys_r, D);
+    if (NS == 0 && gamma_e == 0 && gamma_r == 0)
+      return rescal_step_fused_general(keys_s, keys_r, keys_o, keys_neg_o, N, D, lr, eps);
+    return step_fused_general(
+        name, {{&keys_s, 1}, {&keys_r, 1}, {&keys_o, 1}, {&keys_neg_o, N}, {&keys_neg_s, NS}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          const RescalGroups gr = rescal_groups(res.offs[1], Bh);
+          if (!dev_.is_cuda()) {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            rescal_step_sides_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3],
+                                             res.ptr[4], gr.offs_rg.data(), gr.starts.data(), loss,
+                                             Bh, gr.G, (int)N, (int)NS, (int)D, (float)lr,
+                                             (float)eps, (float)gamma_e, (float)gamma_r);
+            return;
+          }
+          const RescalBlob bl = rescal_blob(name, res, gr);
+          auto scratch = torch::empty({6 * (int64_t)Bh * D + Bh},
+                                      torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+          rescal_step_sides_fused_gpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3], res.ptr[4],
+                                      bl.offs_rg, bl.starts, bl.tiles, bl.n_tiles,
+                                      scratch.data_ptr<float>(), loss, Bh, gr.G, (int)N, (int)NS,
+                                      (int)D, (float)lr, (float)eps, (float)gamma_e,
+                                      (float)gamma_r, current_stream(dev_));
+        });
+  }
+
+  // ---- pieces the two fused RESCAL entries share
+
+  // One entity key role: the array, its keys per sample, and the name the
+  // message gives the role (nullptr: none).
+  struct RescalRole {
+    const torch::Tensor* keys;
+    int64_t per_sample;
+    const char* label;
+  };
+
+  // Argument checks: D, the key budget, every role's count and row length,
+  // and keys_r made of runs of distinct relations.
+  void check_rescal_fused(const char* name, std::initializer_list<RescalRole> ents,
+                          const torch::Tensor& keys_r, int64_t D) {
+    TORCH_CHECK(D >= 4 && D % 4 == 0, name, ": D = ", D, " must be a positive multiple of 4");
+    if (dev_.is_cuda())
+      TORCH_CHECK(D <= RESCAL_FUSED_MAX_DIM, name, ": D = ", D, " exceeds the GPU kernels' limit of ",
+                  RESCAL_FUSED_MAX_DIM);
+    const int64_t B = ents.begin()->keys->numel();
+    std::vector<RescalRole> roles(ents);
+    roles.push_back({&keys_r, 1, "keys_r"});
+    for (auto& r : roles)
+      TORCH_CHECK(B * std::max<int64_t>(r.per_sample, 1) < ((int64_t)1 << 31), name,
+                  ": too many keys in one step");
+    for (size_t a = 0; a < roles.size(); ++a) {
+      const torch::Tensor& t = *roles[a].keys;
+      const bool ent = a + 1 < roles.size();
+      check_keys(t);
+      check_key_range(t);
+      const int64_t n = B * roles[a].per_sample;
+      TORCH_CHECK(t.numel() == n, name, ": key arrays disagree on the batch");
+      const int64_t* kp = t.data_ptr<int64_t>();
+      const int64_t len = ent ? 2 * D : 2 * D * D;
+      const char* label = ent && roles[a].label ? roles[a].label : "";
+      for (int64_t i = 0; i < n; ++i)
+        TORCH_CHECK(len_of(kp[i]) == len, name, ": ", label, *label ? ": " : "", "key ", kp[i],
+                    " has a row of ", len_of(kp[i]), " floats, ", ent ? "an entity" : "a relation",
+                    " row has ", len);
+    }
+    const int64_t* kr = keys_r.data_ptr<int64_t>();
+    std::unordered_set<int64_t> seen;
+    for (int64_t i = 0; i < B; ++i) {
+      if (i && kr[i] == kr[i - 1]) continue;
+      TORCH_CHECK(seen.insert(kr[i]).second, name, ": relation key ", kr[i],
+                  " reappears at position ", i, "; the samples must be sorted by relation");
+    }
+  }
+
+  // The runs of the hit samples' relation offsets
+  struct RescalGroups {
+    std::vector<int64_t> offs_rg;
+    std::vector<int32_t> starts;
+    int G;
+  };
+  static RescalGroups rescal_groups(const std::vector<int64_t>& ro, int Bh) {
+    RescalGroups gr;
+    for (int b = 0; b < Bh; ++b) {
+      if (b && ro[b] == ro[b - 1]) continue;
+      gr.offs_rg.push_back(ro[b]);
+      gr.starts.push_back(b);
+    }
+    gr.starts.push_back(Bh);
+    gr.G = (int)gr.offs_rg.size();
+    return gr;
+  }
+
+  // Device blob offs_rg | starts | tiles, the int32 parts padded to whole words
+  struct RescalBlob {
+    torch::Tensor dev;
+    const int64_t* offs_rg;
+    const int32_t *starts, *tiles;
+    int n_tiles;
+  };
+  RescalBlob rescal_blob(const char* name, const FusedResolve& res, const RescalGroups& gr) {
+    for (auto& o : res.offs)
+      for (int64_t v : o)
+        TORCH_CHECK((v & 3) == 0, name, ": a row does not start on a 16-byte boundary");
+    std::vector<int32_t> tiles;
+    for (int g = 0; g < gr.G; ++g)
+      for (int m0 = 0; m0 < gr.starts[g + 1] - gr.starts[g]; m0 += 16) {
+        tiles.push_back(g);
+        tiles.push_back(m0);
+      }
+    const size_t G = gr.G, w_starts = (gr.starts.size() + 1) / 2, w_tiles = tiles.size() / 2;
+    std::vector<int64_t> blob(G + w_starts + w_tiles, 0);
+    std::memcpy(blob.data(), gr.offs_rg.data(), G * sizeof(int64_t));
+    std::memcpy(blob.data() + G, gr.starts.data(), gr.starts.size() * sizeof(int32_t));
+    std::memcpy(blob.data() + G + w_starts, tiles.data(), tiles.size() * sizeof(int32_t));
+    RescalBlob bl;
+    bl.dev = offs_to_dev(blob);
+    bl.offs_rg = bl.dev.data_ptr<int64_t>();
+    bl.starts = reinterpret_cast<const int32_t*>(bl.offs_rg + G);
+    bl.tiles = reinterpret_cast<const int32_t*>(bl.offs_rg + G + w_starts);
+    bl.n_tiles = (int)w_tiles;
+    return bl;
   }
 
   std::tuple<torch::Tensor, torch::Tensor> w2v_step_fused_general(
@@ -4815,6 +4903,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("kge_step_sides_fused_sampled", &Server::kge_step_sides_fused_sampled,
            py::call_guard<py::gil_scoped_release>())
       .def("kge_step_sides_fused_general", &Server::kge_step_sides_fused_general,
+           py::call_guard<py::gil_scoped_release>())
+      .def("rescal_step_sides_fused_general", &Server::rescal_step_sides_fused_general,
            py::call_guard<py::gil_scoped_release>())
       .def("rescal_step_fused_general", &Server::rescal_step_fused_general,
            py::call_guard<py::gil_scoped_release>())

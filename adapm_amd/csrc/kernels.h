@@ -332,6 +332,54 @@ void rescal_step_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_
                                 const int32_t* starts, float* loss, int B, int G, int N, int D,
                                 float lr, float eps);
 
+// FUSED RESCAL SIDES step (rescal_fused_hip.hip): the two-sided objective of
+// rescal_step_sides above (N object-side negatives o'_j, NS subject-side
+// negatives s'_j, gamma_e on the positive's s and o, gamma_r on its R) on the
+// slab's own rows, with the layout, the arguments and the limits of
+// rescal_step_fused_gpu and the result of rescal_step_sides_grouped: every row
+// occurrence gets ONE AdaGrad update of its summed gradient, dR is the AdaGrad
+// transform of the group-summed gradient, each of a group's Bg positives
+// adding gamma_r R, and loss[b] sums the 1 + N + NS logistic terms without
+// the regulariser.
+//   offs_neg_o [B*N], offs_neg_s [B*NS]  the negatives, in the sorted order
+//   scratch                              6*B*D + B floats, contents irrelevant:
+//                                        U, V, W, Z, Sc, Oc [B][D], then c0 [B]
+// Four launches on `stream`, with u_b = R^T s_b and v_b = R o_b:
+//   1  U = S_g R_g and V = O_g R_g^T over 2 * n_tiles workgroups, s and o
+//      gathered from the slab; Sc[b] = s_b, Oc[b] = o_b
+//   2  per triple, object pass: psi_j = u . o_j, c_j as in the one-sided step,
+//      W[b] = c_0 o + sum_j c_j o'_j, every o'_j updated in place with c_j u,
+//      the positive o scored but NOT written; subject pass: a_j =
+//      sigmoid(v . s'_j), Z[b] = sum_j a_j s'_j, every s'_j updated in place
+//      with a_j v; c0[b], loss[b]
+//   3  s_b += AdaGrad(R_g W[b] + gamma_e Sc[b]) and
+//      o_b += AdaGrad(c0[b] U[b] + R_g^T Z[b] + gamma_e Oc[b]) over 2 * n_tiles
+//      workgroups, from the accumulators
+//   4  R_g += AdaGrad(sum_b (Sc[b] W[b]^T + Z[b] Oc[b]^T) + gamma_r Bg R_g),
+//      one product over the concatenated K = 2 Bg; R is read with a plain
+//      load before the atomics
+// Launch 3 reads the R that launch 4 writes, and launch 4 reads the snapshots
+// Sc and Oc, never the rows launch 3 has moved. Slab writes follow the fused
+// steps' contract given above rescal_step_fused_gpu: atomicAdd of the delta and
+// of g^2, the accumulator read before it with a plain load, hogwild updates
+// for a key named more than once. The loss is summed with softplus1pf, as in
+// every sides kernel (docs/PARITY.md, 2.5). The binding runs
+// rescal_step_fused_gpu / _offs_cpu itself when NS = 0 and both gammas are 0.
+// The CPU twin is serial and in place: per triple it takes copies of s and o,
+// runs both passes on the rows themselves, then updates s and o; R is updated
+// at the end of its group.
+void rescal_step_sides_fused_gpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                 const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                 const int64_t* offs_rg, const int32_t* starts,
+                                 const int32_t* tiles, int n_tiles, float* scratch, float* loss,
+                                 int B, int G, int N, int NS, int D, float lr, float eps,
+                                 float gamma_e, float gamma_r, void* stream);
+void rescal_step_sides_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                      const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                      const int64_t* offs_rg, const int32_t* starts, float* loss,
+                                      int B, int G, int N, int NS, int D, float lr, float eps,
+                                      float gamma_e, float gamma_r);
+
 // word2vec SGNS step: per center/context pair with N negatives.
 //  ctr:  [B][2D] center (syn0) rows;  ctx: [B][2D] context (syn1) rows
 //  neg:  [B*N][2D] negative (syn1) rows

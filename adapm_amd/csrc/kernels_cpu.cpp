@@ -492,6 +492,76 @@ void rescal_step_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_
   }
 }
 
+// Fused RESCAL sides step in place (kernels.h): the twin above with the
+// subject pass against v = R o, the positive o updated after it, and
+// gamma_r * Bg * R added to the group-summed gradient.
+void rescal_step_sides_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                      const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                      const int64_t* offs_rg, const int32_t* starts, float* loss,
+                                      int B, int G, int N, int NS, int D, float lr, float eps,
+                                      float gamma_e, float gamma_r) {
+  const int64_t dd = (int64_t)D * D;
+  std::vector<float> sv(D), ov(D), u(D), v(D), w(D), z(D);
+  std::vector<double> dR(dd);
+  for (int g = 0; g < G; ++g) {
+    float* R = slab + offs_rg[g];
+    std::fill(dR.begin(), dR.end(), 0.0);
+    const int b1 = std::min<int>(starts[g + 1], B);
+    for (int b = starts[g]; b < b1; ++b) {
+      float* sb = slab + offs_s[b];
+      float* pb = slab + offs_o[b];
+      std::copy(sb, sb + D, sv.begin());
+      std::copy(pb, pb + D, ov.begin());
+      for (int j = 0; j < D; ++j) {  // u = R^T s, v = R o
+        double a = 0, c = 0;
+        for (int i = 0; i < D; ++i) {
+          a += R[(int64_t)i * D + j] * sv[i];
+          c += R[(int64_t)j * D + i] * ov[i];
+        }
+        u[j] = (float)a;
+        v[j] = (float)c;
+      }
+      double dot = 0;  // the positive: scored, written after the subject pass
+      for (int k = 0; k < D; ++k) dot += u[k] * ov[k];
+      const float c0 = -sigmoidf_(-(float)dot);
+      float lsum = softplusf_(-(float)dot);
+      for (int k = 0; k < D; ++k) w[k] = c0 * ov[k], z[k] = 0.f;
+      for (int pass = 0; pass < 2; ++pass) {  // o'_j against u into w, s'_j against v into z
+        const std::vector<float>& x = pass ? v : u;
+        std::vector<float>& sum = pass ? z : w;
+        const int n = pass ? NS : N;
+        const int64_t* offs = pass ? offs_neg_s + (int64_t)b * NS : offs_neg_o + (int64_t)b * N;
+        for (int j = 0; j < n; ++j) {
+          float* xb = slab + offs[j];
+          dot = 0;
+          for (int k = 0; k < D; ++k) dot += x[k] * xb[k];
+          const float c = sigmoidf_((float)dot);
+          lsum += softplusf_((float)dot);
+          for (int k = 0; k < D; ++k) {
+            sum[k] += c * xb[k];
+            adagrad_inplace(xb[k], xb[D + k], c * x[k], lr, eps);
+          }
+        }
+      }
+      loss[b] = lsum;
+      // ds = R w + gamma_e s, do = c0 u + R^T z + gamma_e o, dR += s w^T + z o^T
+      for (int i = 0; i < D; ++i) {
+        double a = 0, c = 0;
+        for (int k = 0; k < D; ++k) {
+          a += R[(int64_t)i * D + k] * w[k];
+          c += R[(int64_t)k * D + i] * z[k];
+          dR[(int64_t)i * D + k] += (double)sv[i] * w[k] + (double)z[i] * ov[k];
+        }
+        adagrad_inplace(sb[i], sb[D + i], (float)a + gamma_e * sv[i], lr, eps);
+        adagrad_inplace(pb[i], pb[D + i], c0 * u[i] + (float)c + gamma_e * ov[i], lr, eps);
+      }
+    }
+    const float gr = gamma_r * (float)(b1 - starts[g]);
+    for (int64_t i = 0; i < dd; ++i)
+      adagrad_inplace(R[i], R[dd + i], (float)dR[i] + gr * R[i], lr, eps);
+  }
+}
+
 void mf_loss_cpu(const float* w, const float* h, const float* x, float* out2, int B, int R,
                  float lambda) {
   const int row = R << 1;

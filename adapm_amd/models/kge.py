@@ -512,7 +512,7 @@ class Rescal(StepModel):
     objective of ComplExConfig (neg_samples_subject, gamma_entity,
     gamma_relation) selects rescal_step_sides / rescal_step_sides_grouped.
     train_batch_fused is the opt-in slab-direct step of the one-sided
-    objective."""
+    objective and, with fuse_sides=True, of the two-sided one."""
 
     @staticmethod
     def value_lengths(num_entities, num_relations, dim):
@@ -633,26 +633,35 @@ class Rescal(StepModel):
     # ----------------------------------------------------- fused step
 
     def train_batch_fused(self, triples: np.ndarray, sync_loss: bool = False,
-                          force_general: bool = False, neg_keys: np.ndarray = None):
+                          force_general: bool = False, neg_keys: np.ndarray = None,
+                          fuse_sides: bool = False):
         """Fused slab-direct step (Server.rescal_step_fused_general): the
         kernels gather s from the slab, update o and the negatives where
         they score them and write the AdaGrad updates of s and R from
-        the MFMA accumulators; no pulled or delta buffer. One-sided
-        objective only: with cfg.sides, off the GPU (unless
-        force_general, which runs the general path on a CPU store), and
-        for a dim the kernels do not take, this is train_batch. Samples
-        with a key that is not local go through train_batch as well,
-        deferred by one step first (StepModel._fused_step). neg_keys as
-        in train_batch."""
+        the MFMA accumulators; no pulled or delta buffer. With cfg.sides
+        the step is train_batch unless fuse_sides, which selects the
+        two-sided fused step (Server.rescal_step_sides_fused_general:
+        subject-side negatives and the L2 terms in the same four
+        launches). Off the GPU (unless force_general, which runs the
+        general path on a CPU store) and for a dim the kernels do not
+        take, this is train_batch as well. Samples with a key that is
+        not local go through train_batch, deferred by one step first
+        (StepModel._fused_step). neg_keys as in train_batch: with
+        cfg.sides the first B * neg_samples keys corrupt the object and
+        the rest the subject."""
         cfg = self.cfg
-        if (cfg.sides or (self.dev.type != "cuda" and not force_general)
+        if ((cfg.sides and not fuse_sides) or (self.dev.type != "cuda" and not force_general)
                 or cfg.dim % 4 or cfg.dim > _C.RESCAL_FUSED_MAX_DIM):
             return self.train_batch(triples, sync_loss=sync_loss, neg_keys=neg_keys)
-        B = len(triples)
+        B, N = len(triples), cfg.neg_samples
+        NS = cfg.neg_samples_subject if cfg.sides else 0
         if neg_keys is None:
-            neg_keys = self._negatives(B * cfg.neg_samples, cfg.num_entities)
-        negs2 = np.ascontiguousarray(neg_keys, dtype=np.int64).reshape(B, cfg.neg_samples)
-        return self._fused_step((triples, negs2), sync_loss, force_general)
+            neg_keys = self._negatives(B * (N + NS), cfg.num_entities)
+        neg_keys = np.ascontiguousarray(neg_keys, dtype=np.int64)
+        arrays = (triples, neg_keys[:B * N].reshape(B, N))
+        if cfg.sides:
+            arrays += (neg_keys[B * N:].reshape(B, NS),)
+        return self._fused_step(arrays, sync_loss, force_general)
 
     def _fused_identity(self, force_general):
         return False  # no identity layout for two value lengths
@@ -660,20 +669,29 @@ class Rescal(StepModel):
     def _fused_general_step(self, arrays):
         """The kernels want the samples in runs of one relation; deferred
         samples sit in front of the batch, so sort here. `missed` comes
-        back as positions in the sorted order."""
+        back as positions in the sorted order. Three arrays (a second one
+        of negatives, the subject-side ones) mean the two-sided step."""
         cfg = self.cfg
-        triples, negs2 = arrays
+        triples = arrays[0]
         order = np.argsort(triples[:, 1], kind="stable")
         t = triples[order]
-        keys = (t[:, 0], cfg.num_entities + t[:, 1], t[:, 2], negs2[order].reshape(-1))
-        loss, missed = self.server.raw.rescal_step_fused_general(
-            *(torch.from_numpy(np.ascontiguousarray(k, dtype=np.int64)) for k in keys),
-            cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
+        keys = (t[:, 0], cfg.num_entities + t[:, 1], t[:, 2]) + tuple(
+            n[order].reshape(-1) for n in arrays[1:])
+        keys = [torch.from_numpy(np.ascontiguousarray(k, dtype=np.int64)) for k in keys]
+        if len(arrays) == 3:
+            loss, missed = self.server.raw.rescal_step_sides_fused_general(
+                *keys, cfg.neg_samples, cfg.neg_samples_subject, cfg.dim, cfg.lr, cfg.eps,
+                cfg.gamma_entity, cfg.gamma_relation)
+        else:
+            loss, missed = self.server.raw.rescal_step_fused_general(
+                *keys, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
         return loss, torch.from_numpy(order[missed.numpy()])
 
     def _classic_step(self, arrays):
-        triples, negs2 = arrays
-        return self.train_batch(triples, sync_loss=False, neg_keys=negs2.reshape(-1))
+        """train_batch on (deferred or missed) samples, the negatives back in
+        its layout: all object-side keys, then all subject-side ones."""
+        neg = np.concatenate([n.reshape(-1) for n in arrays[1:]])
+        return self.train_batch(arrays[0], sync_loss=False, neg_keys=neg)
 
     @staticmethod
     def _by_sample(keys, B, n, order):

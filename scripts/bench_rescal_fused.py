@@ -10,6 +10,11 @@ Both paths run the same batches with the same pre-drawn negatives, in the
 order F C C F, twice, in one process; every run and the medians are printed,
 then one JSON line.
 
+--neg-samples-subject, --gamma-entity or --gamma-relation off their defaults
+select the two-sided objective: the F runs are the two-sided fused step
+(train_batch_fused(fuse_sides=True)), the C runs the two-sided classic step
+(ten launches around five pulls and five pushes).
+
 Run on a GPU box:  python scripts/bench_rescal_fused.py [--dim 128] [--batch 2048]
 """
 import argparse
@@ -32,6 +37,9 @@ def main():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--neg", type=int, default=8)
+    ap.add_argument("--neg-samples-subject", type=int, default=0)
+    ap.add_argument("--gamma-entity", type=float, default=0.0)
+    ap.add_argument("--gamma-relation", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--order", type=str, default="FCCFFCCF",
@@ -43,7 +51,10 @@ def main():
     from adapm_amd.models.kge import ComplExConfig, Rescal
 
     E, R, D, B, N = args.entities, args.relations, args.dim, args.batch, args.neg
-    cfg = ComplExConfig(num_entities=E, num_relations=R, dim=D, neg_samples=N, batch_size=B)
+    NS = args.neg_samples_subject
+    cfg = ComplExConfig(num_entities=E, num_relations=R, dim=D, neg_samples=N, batch_size=B,
+                        neg_samples_subject=NS, gamma_entity=args.gamma_entity,
+                        gamma_relation=args.gamma_relation)
     adapm_amd.setup(num_keys=E + R, num_threads=1, device="cuda:0")
     server = adapm_amd.Server(torch.from_numpy(Rescal.value_lengths(E, R, D)))
     worker = adapm_amd.Worker(0, server)
@@ -54,13 +65,13 @@ def main():
     total = args.warmup + args.steps
     batches = [(np.stack([rng.integers(0, E, B), rng.integers(0, R, B), rng.integers(0, E, B)],
                          axis=1).astype(np.int64),
-                rng.integers(0, E, B * N, dtype=np.int64)) for _ in range(total)]
+                rng.integers(0, E, B * (N + NS), dtype=np.int64)) for _ in range(total)]
 
     def classic(t, neg):
         model.train_batch(t, sync_loss=False, grouped=True, neg_keys=neg)
 
     def fused(t, neg):
-        model.train_batch_fused(t, sync_loss=False, neg_keys=neg)
+        model.train_batch_fused(t, sync_loss=False, neg_keys=neg, fuse_sides=True)
 
     def run(step):
         for t, neg in batches[:args.warmup]:
@@ -81,12 +92,15 @@ def main():
     med = {k: statistics.median(v) if v else float("nan") for k, v in ms.items()}
     print(f"median: classic {med['classic']:.3f} ms, fused {med['fused']:.3f} ms, "
           f"classic / fused = {med['classic'] / med['fused']:.2f}x "
-          f"(E={E}, R={R}, D={D}, B={B}, N={N})")
+          f"(E={E}, R={R}, D={D}, B={B}, N={N}, NS={NS}, gamma_e={args.gamma_entity:g}, "
+          f"gamma_r={args.gamma_relation:g})")
     print(json.dumps({"metric": "rescal_step_ms", "classic_ms": ms["classic"],
                       "fused_ms": ms["fused"], "classic_median_ms": med["classic"],
                       "fused_median_ms": med["fused"],
                       "ratio": med["classic"] / med["fused"],
                       "config": {"entities": E, "relations": R, "dim": D, "batch": B, "neg": N,
+                                 "neg_subject": NS, "gamma_entity": args.gamma_entity,
+                                 "gamma_relation": args.gamma_relation,
                                  "steps": args.steps, "warmup": args.warmup}}), flush=True)
     worker.finalize()
     server.shutdown()

@@ -88,6 +88,15 @@ static void check_step_lanes(const char* name, const char* what, int64_t lanes) 
               " exceeds the GPU step kernels' limit of ", STEP_MAX_LANES);
 }
 
+// Dropout probabilities of the ComplEx drop step -> 10-bit thresholds
+// (kernels.h): refused unless lround(p * 1024) lies in [0, 1023].
+static std::pair<int, int> check_drop(const char* name, double p_e, double p_r) {
+  const int thr_e = drop_threshold(p_e), thr_r = drop_threshold(p_r);
+  TORCH_CHECK(thr_e >= 0 && thr_r >= 0, name, ": dropout p_e = ", p_e, ", p_r = ", p_r,
+              " must round to a multiple of 1/1024 in [0, 1023/1024]");
+  return {thr_e, thr_r};
+}
+
 // ---------------------------------------------------------------- slab
 
 // Flat float32 value arena with size-class free lists. Slot sizes are
@@ -3126,6 +3135,102 @@ class Server {
                                      lr, eps, gamma_e, gamma_r);
   }
 
+  // The sides step with dropout (kernels.h, kge_complex_step_drop) on the
+  // identity path: kge_step_sides_fused_impl pass for pass (the staged key
+  // upload that is the tag pass, flag pass, bits pass, step), with the two
+  // thresholds checked beside the other arguments before the store is looked
+  // at. A separate body for the reason given there.
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_drop_fused_impl(
+      const torch::Tensor& keys_s, const torch::Tensor& keys_r, const torch::Tensor& keys_o,
+      const torch::Tensor* keys_neg_o, const torch::Tensor* keys_neg_s, UniformStream* us,
+      int64_t N, int64_t NS, int64_t D, double lr, double eps, double gamma_e, double gamma_r,
+      double p_e, double p_r, uint64_t drop_seed) {
+    const char* name = us ? "kge_step_drop_fused_sampled" : "kge_step_drop_fused";
+    check_step_lanes(name, "D/2", D / 2);
+    const auto thr = check_drop(name, p_e, p_r);
+    TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+    const int64_t B = keys_s.numel();
+    TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B, name,
+                ": key arrays disagree on the batch");
+    // the tag pass numbers the occurrences in 32 bits, ROWTAG_SHARED aside
+    TORCH_CHECK(N < (int64_t)ROWTAG_SHARED && NS < (int64_t)ROWTAG_SHARED &&
+                    (3 + N + NS) * B < (int64_t)ROWTAG_SHARED,
+                name, ": too many keys in one step");
+    if (!us)
+      TORCH_CHECK(keys_neg_o->numel() == B * N && keys_neg_s->numel() == B * NS, name,
+                  ": key arrays disagree on the batch");
+    check_fused_identity(name, D);
+    HostKeys hk;
+    StagedKeys sk;
+    torch::Tensor drawn;
+    const int64_t *kno = nullptr, *kns = nullptr;
+    if (us) {
+      TORCH_CHECK(us->lo() >= 0 && us->hi() <= num_keys_, name, ": stream range [", us->lo(),
+                  ", ", us->hi(), ") exceeds the store's ", num_keys_, " keys");
+      TORCH_CHECK(us->device() == dev_, name, ": stream is not on the store's device");
+      TORCH_CHECK(B * (N + NS) > 0, name, ": nothing to draw");
+      hk = host_keys({&keys_s, &keys_r, &keys_o});
+      // one draw: the first B*N keys are object-side, the rest subject-side
+      drawn = us->draw(B * (N + NS));
+      kno = drawn.data_ptr<int64_t>();
+      kns = kno + B * N;
+    } else {
+      hk = host_keys({&keys_s, &keys_r, &keys_o, keys_neg_o, keys_neg_s});
+    }
+    const int64_t n_dev = us ? B * (N + NS) : 0;
+
+    auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    void* st = current_stream(dev_);
+    {
+      InflightGuard g(this);
+      std::unique_lock<std::mutex> mg(fused_mu_);  // see kge_step_fused_impl
+      const bool plain = fused_plain_ok(st);
+      uint32_t *tags = nullptr, *bits = nullptr;
+      if (plain) {
+        tags = reinterpret_cast<uint32_t*>(fused_tags_.data_ptr<int32_t>());
+        bits = tags + 32 * rowtag_words(num_keys_);
+      } else {
+        mg.unlock();
+      }
+      sk = upload_keys(name, hk, tags, kno, n_dev);
+      if (!us) kno = sk.ptr[3], kns = sk.ptr[4];
+      if (plain) {
+        RowTagKeys tk{{sk.ptr[0], kno, nullptr, nullptr}, {hk.blob.numel(), n_dev, 0, 0}, 2};
+        rowtag_flag_gpu(tags, tk, st);
+        rowtag_bits_gpu(tags, bits, tk, st);
+      }
+      kge_complex_step_drop_fused_gpu(
+          slab_.data, sk.ptr[0], sk.ptr[1], sk.ptr[2], kno, kns, loss.data_ptr<float>(), (int)B,
+          (int)N, (int)NS, (int)D, Slab::padded(uniform_len_), world_, (float)lr, (float)eps,
+          (float)gamma_e, (float)gamma_r, thr.first, thr.second, drop_seed, st, bits,
+          plain && fused_shared_stat_.defined()
+              ? reinterpret_cast<unsigned long long*>(fused_shared_stat_.data_ptr<int64_t>())
+              : nullptr);
+      (plain ? stat_fused_plain_ : stat_fused_atomic_) += 1;
+    }
+    count_fused_ops(3 * B + B * (N + NS));
+    return {loss, drawn};
+  }
+
+  torch::Tensor kge_step_drop_fused(torch::Tensor keys_s, torch::Tensor keys_r,
+                                    torch::Tensor keys_o, torch::Tensor keys_neg_o,
+                                    torch::Tensor keys_neg_s, int64_t N, int64_t NS, int64_t D,
+                                    double lr, double eps, double gamma_e, double gamma_r,
+                                    double p_e, double p_r, uint64_t drop_seed) {
+    return std::get<0>(kge_step_drop_fused_impl(keys_s, keys_r, keys_o, &keys_neg_o, &keys_neg_s,
+                                                nullptr, N, NS, D, lr, eps, gamma_e, gamma_r, p_e,
+                                                p_r, drop_seed));
+  }
+
+  // Returns (loss, the B*(N+NS) drawn keys on the device, object-side first).
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_drop_fused_sampled(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, UniformStream& us,
+      int64_t N, int64_t NS, int64_t D, double lr, double eps, double gamma_e, double gamma_r,
+      double p_e, double p_r, uint64_t drop_seed) {
+    return kge_step_drop_fused_impl(keys_s, keys_r, keys_o, nullptr, nullptr, &us, N, NS, D, lr,
+                                    eps, gamma_e, gamma_r, p_e, p_r, drop_seed);
+  }
+
   // ---- fused slab-direct steps at world>1 / relocated layouts --------
   //
   // The identity-layout fused step above requires world==1. At world>1
@@ -3313,6 +3418,39 @@ class Server {
             kge_complex_step_sides_fused_offs_cpu(
                 slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], res.ptr[3], res.ptr[4], loss, Bh,
                 (int)N, (int)NS, (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r);
+          }
+        });
+  }
+
+  // The sides step with dropout on the general path (CPU store included).
+  // The masks are indexed by a sample's position among the HIT samples, in
+  // the compacted arrays the step runs on.
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_drop_fused_general(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, torch::Tensor keys_neg_o,
+      torch::Tensor keys_neg_s, int64_t N, int64_t NS, int64_t D, double lr, double eps,
+      double gamma_e, double gamma_r, double p_e, double p_r, uint64_t drop_seed) {
+    const char* name = "kge_step_drop_fused";
+    const auto thr = check_drop(name, p_e, p_r);
+    TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+    TORCH_CHECK(uniform_len_ == 2 * D, name, ": store rows must be [emb|accum] = 2D");
+    if (dev_.is_cuda()) check_step_lanes(name, "D/2", D / 2);
+    return step_fused_general(
+        name,
+        {{&keys_s, 1}, {&keys_r, 1}, {&keys_o, 1}, {&keys_neg_o, N}, {&keys_neg_s, NS}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          if (dev_.is_cuda()) {
+            kge_complex_step_drop_fused_gpu(
+                slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], res.ptr[3], res.ptr[4], loss, Bh,
+                (int)N, (int)NS, (int)D, Slab::padded(uniform_len_), /*world=offsets-mode*/ 0,
+                (float)lr, (float)eps, (float)gamma_e, (float)gamma_r, thr.first, thr.second,
+                drop_seed, current_stream(dev_));
+          } else {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            kge_complex_step_drop_fused_offs_cpu(
+                slab_.data, res.ptr[0], res.ptr[1], res.ptr[2], res.ptr[3], res.ptr[4], loss, Bh,
+                (int)N, (int)NS, (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r,
+                thr.first, thr.second, drop_seed);
           }
         });
   }
@@ -4225,6 +4363,44 @@ void kge_complex_step_sides(torch::Tensor s, torch::Tensor r, torch::Tensor o,
   }
 }
 
+// ComplEx sides step with dropout (kernels.h): the sides step's tensors and
+// checks, plus the two dropout probabilities and the seed of the masks.
+void kge_complex_step_drop(torch::Tensor s, torch::Tensor r, torch::Tensor o,
+                           torch::Tensor neg_o, torch::Tensor neg_s, torch::Tensor ds,
+                           torch::Tensor dr, torch::Tensor do_, torch::Tensor dneg_o,
+                           torch::Tensor dneg_s, torch::Tensor loss, int64_t N, int64_t NS,
+                           int64_t D, double lr, double eps, double gamma_e, double gamma_r,
+                           double p_e, double p_r, uint64_t drop_seed) {
+  const char* name = "kge_complex_step_drop";
+  for (auto* t : {&s, &r, &o, &neg_o, &neg_s, &ds, &dr, &do_, &dneg_o, &dneg_s, &loss}) {
+    check_f32(*t, "kge tensor");
+    TORCH_CHECK(t->device() == s.device(), name, ": tensors on different devices");
+  }
+  const auto thr = check_drop(name, p_e, p_r);
+  TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+  TORCH_CHECK(D >= 2 && D % 2 == 0, name, ": D = ", D, " must be even and >= 2");
+  const int64_t B = loss.numel(), row = 2 * D;
+  for (auto* t : {&s, &r, &o, &ds, &dr, &do_})
+    TORCH_CHECK(t->numel() == B * row, name, ": s, r, o and their deltas must be [B][2D]");
+  for (auto* t : {&neg_o, &dneg_o})
+    TORCH_CHECK(t->numel() == B * N * row, name, ": neg_o and dneg_o must be [B*N][2D]");
+  for (auto* t : {&neg_s, &dneg_s})
+    TORCH_CHECK(t->numel() == B * NS * row, name, ": neg_s and dneg_s must be [B*NS][2D]");
+  if (s.is_cuda()) {
+    TORCH_CHECK(hip_available(), name, ": CUDA tensor but no HIP device");
+    check_step_lanes(name, "D/2", D / 2);
+    kge_complex_step_drop_gpu(cfp(s), cfp(r), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(dr),
+                              fp(do_), fp(dneg_o), fp(dneg_s), fp(loss), (int)B, (int)N, (int)NS,
+                              (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r,
+                              thr.first, thr.second, drop_seed, current_stream(s.device()));
+  } else {
+    kge_complex_step_drop_cpu(cfp(s), cfp(r), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(dr),
+                              fp(do_), fp(dneg_o), fp(dneg_s), fp(loss), (int)B, (int)N, (int)NS,
+                              (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r,
+                              thr.first, thr.second, drop_seed);
+  }
+}
+
 void rescal_step(torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::Tensor neg,
                  torch::Tensor ds, torch::Tensor drl, torch::Tensor do_, torch::Tensor dneg,
                  torch::Tensor loss, int64_t N, int64_t D, double lr, double eps) {
@@ -4813,6 +4989,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kge_complex_step", &kge_complex_step, py::call_guard<py::gil_scoped_release>());
   m.def("kge_complex_step_sides", &kge_complex_step_sides,
         py::call_guard<py::gil_scoped_release>());
+  m.def("kge_complex_step_drop", &kge_complex_step_drop,
+        py::call_guard<py::gil_scoped_release>());
   m.def("alias_draw", &alias_draw, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step", &rescal_step, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_grouped", &rescal_step_grouped, py::call_guard<py::gil_scoped_release>());
@@ -4903,6 +5081,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("kge_step_sides_fused_sampled", &Server::kge_step_sides_fused_sampled,
            py::call_guard<py::gil_scoped_release>())
       .def("kge_step_sides_fused_general", &Server::kge_step_sides_fused_general,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_drop_fused", &Server::kge_step_drop_fused,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_drop_fused_sampled", &Server::kge_step_drop_fused_sampled,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_drop_fused_general", &Server::kge_step_drop_fused_general,
            py::call_guard<py::gil_scoped_release>())
       .def("rescal_step_sides_fused_general", &Server::rescal_step_sides_fused_general,
            py::call_guard<py::gil_scoped_release>())

@@ -59,8 +59,8 @@ void kge_complex_step_cpu(const float* s, const float* r, const float* o, const 
 //  positives only). The regulariser's value is not part of loss[b].
 // With NS = 0 and both gammas 0 this is kge_complex_step, in its order of
 // operations; the GPU launchers (classic and fused) then run the one-sided
-// kernel itself, which is what makes the results the same bit for bit. No
-// dropout (off by default in the reference).
+// kernel itself, which is what makes the results the same bit for bit.
+// Dropout is kge_complex_step_drop, further down.
 void kge_complex_step_sides_gpu(const float* s, const float* r, const float* o,
                                 const float* neg_o, const float* neg_s, float* ds, float* dr,
                                 float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
@@ -160,6 +160,72 @@ void kge_complex_step_sides_fused_offs_cpu(float* slab, const int64_t* offs_s,
                                            const int64_t* offs_neg_o, const int64_t* offs_neg_s,
                                            float* loss, int B, int N, int NS, int D, float lr,
                                            float eps, float gamma_e, float gamma_r);
+
+// ComplEx sides step WITH DROPOUT (kge_drop_hip.hip; reference do_dropout in
+// train(), --dropout_entity / --dropout_relation). One sample is the sides
+// step's: a positive (s, r, o), N object-side negatives (s, r, o'_j), NS
+// subject-side negatives (s'_j, r, o). Its scored triples are numbered
+//   t = 0             the positive
+//   t = 1 .. N        the object-side negatives
+//   t = N+1 .. N+NS   the subject-side negatives,        T = 1 + N + NS
+// and every scored triple draws fresh masks for each of its three rows, over
+// the D embedding floats (real and imaginary halves independently), never
+// over the accumulators:
+//   psi_t = psi(m_s,t * s_t, m_r,t * r, m_o,t * o_t),  mask values 0 or scale.
+// loss[b] sums the same 1 + N + NS logistic terms (softplus1pf on the GPU).
+// The gradient is the true gradient of that loss: a dropped component gets no
+// score gradient from that triple (an exact 0), a kept one `scale` times the
+// gradient with respect to the masked value. gamma_e and gamma_r act on the
+// STORED rows of the positive and every row occurrence gets ONE AdaGrad update
+// of its summed gradient, exactly as in the sides step.
+// Mask. For complex lane k < dc = D/2 of triple t of sample b (b = position in
+// THIS call's arrays; on the general path, in the compacted ones), in 64 bits:
+//   idx = (b * T + t) * dc + k
+//   h   = pcg_hash64(drop_seed ^ idx * 0x9e3779b97f4a7c15)   (as alias_draw)
+// Field f = bits [10f, 10f + 10) of h, f = 0..5 = (s_re, s_im, r_re, r_im,
+// o_re, o_im), where s / o name the ROLE in the scored triple (s'_j takes the
+// s fields, o'_j the o fields). A component is kept iff its field >= thr:
+//   thr_e = lround(p_e * 1024) for the s and o fields, thr_r likewise from p_r,
+//   both in [0, 1023] (drop_threshold; the bindings check);
+//   scale = 1024 / (1024 - thr) rounded to fp32 (drop_scale), the reciprocal
+//   of the keep probability actually realised.
+// One hash per complex lane per triple yields all six masks; nothing about a
+// mask is stored. With thr_e == thr_r == 0 the entry points run the sides
+// entry points themselves (bit-equal results, docs/PARITY.md 2.5). The fused
+// step has the addressing modes, the `bits` contract (tags over all five key
+// arrays) and shared_stat of kge_complex_step_sides_fused_gpu. The CPU twins
+// are serial; the fused one works in place in the fused kernel's order.
+// Unlike the reference, the gradient is chained through the mask and the
+// regulariser sees the stored values (docs/PARITY.md 2.3).
+constexpr int DROP_FIELD_BITS = 10;
+constexpr int DROP_ONE = 1 << DROP_FIELD_BITS;  // 1024
+int drop_threshold(double p);  // lround(p * 1024), or -1 if that is not in [0, 1023]
+inline float drop_scale(int thr) { return (float)((double)DROP_ONE / (DROP_ONE - thr)); }
+void kge_complex_step_drop_gpu(const float* s, const float* r, const float* o,
+                               const float* neg_o, const float* neg_s, float* ds, float* dr,
+                               float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
+                               int N, int NS, int D, float lr, float eps, float gamma_e,
+                               float gamma_r, int thr_e, int thr_r, uint64_t drop_seed,
+                               void* stream);
+void kge_complex_step_drop_cpu(const float* s, const float* r, const float* o,
+                               const float* neg_o, const float* neg_s, float* ds, float* dr,
+                               float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
+                               int N, int NS, int D, float lr, float eps, float gamma_e,
+                               float gamma_r, int thr_e, int thr_r, uint64_t drop_seed);
+void kge_complex_step_drop_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
+                                     const int64_t* keys_o, const int64_t* keys_neg_o,
+                                     const int64_t* keys_neg_s, float* loss, int B, int N, int NS,
+                                     int D, int32_t plen, int world, float lr, float eps,
+                                     float gamma_e, float gamma_r, int thr_e, int thr_r,
+                                     uint64_t drop_seed, void* stream,
+                                     const uint32_t* bits = nullptr,
+                                     unsigned long long* shared_stat = nullptr);
+void kge_complex_step_drop_fused_offs_cpu(float* slab, const int64_t* offs_s,
+                                          const int64_t* offs_r, const int64_t* offs_o,
+                                          const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                          float* loss, int B, int N, int NS, int D, float lr,
+                                          float eps, float gamma_e, float gamma_r, int thr_e,
+                                          int thr_r, uint64_t drop_seed);
 
 // CPU tier of the offsets-mode fused steps (exercises the world>1 fused
 // protocol path in the gloo multi-process tests; serial, in-place).

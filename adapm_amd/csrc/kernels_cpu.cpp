@@ -599,6 +599,133 @@ void alias_draw_cpu(const float* prob, const int32_t* alias, int64_t n, uint64_t
   }
 }
 
+// ---- ComplEx sides step with dropout (kernels.h, kge_complex_step_drop)
+
+int drop_threshold(double p) {
+  if (!(p >= 0.0 && p <= 1.0)) return -1;
+  const long t = std::lround(p * DROP_ONE);
+  return t < DROP_ONE ? (int)t : -1;
+}
+
+// One sample after the other, in the order of the kernels: the object pass
+// (t = 0 the positive, then o'_j, each updated as it is scored), s, the
+// positive o read again, the subject pass, r and o. row(role, i) is the i-th
+// row [emb(D) | acc(D)] of role s, r, o, neg_o, neg_s = 0..4 and
+// upd(role, i, g) applies the AdaGrad update of gradient g[D] to it; vectors
+// are laid out as the rows are, [re(dc) | im(dc)].
+template <typename Row, typename Upd>
+static void drop_step_serial(Row row, Upd upd, float* loss, int B, int N, int NS, int D,
+                             float gamma_e, float gamma_r, int thr_e, int thr_r, uint64_t seed) {
+  const int dc = D >> 1;
+  const uint64_t T = 1 + (uint64_t)N + (uint64_t)NS;
+  const float sc_e = drop_scale(thr_e), sc_r = drop_scale(thr_r);
+  std::vector<float> a_s(D), a_r(D), a_o(D), sv(D), rv(D), pv(D), gx(D), gr(D), gy(D);
+  std::vector<float> m(3 * D);  // m_s | m_r | m_o: field f of lane k at m[f * dc + k]
+  const float *m_s = m.data(), *m_r = m_s + D, *m_o = m_r + D;
+  float lsum = 0.f;
+  // scores triple t of sample b, (x, rv, y) with label yl, adds its loss term
+  // and leaves the gradients of its three rows in gx, gr, gy
+  auto score = [&](uint64_t b, uint64_t t, const float* x, const float* y, float yl) {
+    for (int k = 0; k < dc; ++k) {
+      const uint64_t idx = (b * T + t) * (uint64_t)dc + (uint64_t)k;
+      const uint64_t h = pcg_hash64_c(seed ^ idx * 0x9e3779b97f4a7c15ULL);
+      for (int f = 0; f < 6; ++f) {
+        const bool rel = f == 2 || f == 3;
+        const uint32_t field = (uint32_t)(h >> (DROP_FIELD_BITS * f)) & (DROP_ONE - 1);
+        m[f * dc + k] = field >= (uint32_t)(rel ? thr_r : thr_e) ? (rel ? sc_r : sc_e) : 0.f;
+      }
+    }
+    double psi = 0.0;
+    for (int k = 0; k < dc; ++k) {
+      const float x_re = m_s[k] * x[k], x_im = m_s[dc + k] * x[dc + k];
+      const float r_re = m_r[k] * rv[k], r_im = m_r[dc + k] * rv[dc + k];
+      const float y_re = m_o[k] * y[k], y_im = m_o[dc + k] * y[dc + k];
+      gy[k] = x_re * r_re - x_im * r_im;
+      gy[dc + k] = x_im * r_re + x_re * r_im;
+      psi += gy[k] * y_re + gy[dc + k] * y_im;
+      gx[k] = r_re * y_re + r_im * y_im;
+      gx[dc + k] = r_re * y_im - r_im * y_re;
+      gr[k] = x_re * y_re + x_im * y_im;
+      gr[dc + k] = x_re * y_im - x_im * y_re;
+    }
+    const float c = -yl * sigmoidf_(-yl * (float)psi);
+    lsum += softplusf_(-yl * (float)psi);
+    for (int i = 0; i < D; ++i) {
+      gx[i] *= c * m_s[i];
+      gr[i] *= c * m_r[i];
+      gy[i] *= c * m_o[i];
+    }
+  };
+  for (int b = 0; b < B; ++b) {
+    std::copy(row(0, b), row(0, b) + D, sv.begin());
+    std::copy(row(1, b), row(1, b) + D, rv.begin());
+    std::fill(a_s.begin(), a_s.end(), 0.f);
+    std::fill(a_r.begin(), a_r.end(), 0.f);
+    lsum = 0.f;
+    for (int j = 0; j <= N; ++j) {
+      const int64_t jo = (int64_t)b * N + (j - 1);
+      score(b, j, sv.data(), j == 0 ? row(2, b) : row(3, jo), j == 0 ? 1.f : -1.f);
+      for (int i = 0; i < D; ++i) a_s[i] += gx[i], a_r[i] += gr[i];
+      if (j == 0) a_o = gy;  // the positive object waits for the subject pass
+      else upd(3, jo, gy.data());
+    }
+    for (int i = 0; i < D; ++i) a_s[i] += gamma_e * sv[i];
+    upd(0, b, a_s.data());
+    std::copy(row(2, b), row(2, b) + D, pv.begin());
+    for (int j = 0; j < NS; ++j) {
+      const int64_t js = (int64_t)b * NS + j;
+      score(b, N + 1 + j, row(4, js), pv.data(), -1.f);
+      for (int i = 0; i < D; ++i) a_r[i] += gr[i], a_o[i] += gy[i];
+      upd(4, js, gx.data());
+    }
+    for (int i = 0; i < D; ++i) a_r[i] += gamma_r * rv[i], a_o[i] += gamma_e * pv[i];
+    upd(1, b, a_r.data());
+    upd(2, b, a_o.data());
+    loss[b] = lsum;
+  }
+}
+
+void kge_complex_step_drop_cpu(const float* s, const float* r, const float* o,
+                               const float* neg_o, const float* neg_s, float* ds, float* dr,
+                               float* do_, float* dneg_o, float* dneg_s, float* loss, int B,
+                               int N, int NS, int D, float lr, float eps, float gamma_e,
+                               float gamma_r, int thr_e, int thr_r, uint64_t drop_seed) {
+  if (thr_e == 0 && thr_r == 0)  // no dropout is the sides step itself
+    return kge_complex_step_sides_cpu(s, r, o, neg_o, neg_s, ds, dr, do_, dneg_o, dneg_s, loss, B,
+                                      N, NS, D, lr, eps, gamma_e, gamma_r);
+  const float* in[5] = {s, r, o, neg_o, neg_s};
+  float* out[5] = {ds, dr, do_, dneg_o, dneg_s};
+  const int64_t rowlen = 2 * (int64_t)D;
+  drop_step_serial(
+      [&](int role, int64_t i) { return in[role] + i * rowlen; },
+      [&](int role, int64_t i, const float* g) {
+        const float* v = in[role] + i * rowlen;
+        float* d = out[role] + i * rowlen;
+        for (int q = 0; q < D; ++q) write_delta_(&d[q], &d[D + q], g[q], v[D + q], lr, eps);
+      },
+      loss, B, N, NS, D, gamma_e, gamma_r, thr_e, thr_r, drop_seed);
+}
+
+void kge_complex_step_drop_fused_offs_cpu(float* slab, const int64_t* offs_s,
+                                          const int64_t* offs_r, const int64_t* offs_o,
+                                          const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                          float* loss, int B, int N, int NS, int D, float lr,
+                                          float eps, float gamma_e, float gamma_r, int thr_e,
+                                          int thr_r, uint64_t drop_seed) {
+  if (thr_e == 0 && thr_r == 0)
+    return kge_complex_step_sides_fused_offs_cpu(slab, offs_s, offs_r, offs_o, offs_neg_o,
+                                                 offs_neg_s, loss, B, N, NS, D, lr, eps, gamma_e,
+                                                 gamma_r);
+  const int64_t* offs[5] = {offs_s, offs_r, offs_o, offs_neg_o, offs_neg_s};
+  drop_step_serial(
+      [&](int role, int64_t i) { return slab + offs[role][i]; },
+      [&](int role, int64_t i, const float* g) {
+        float* v = slab + offs[role][i];
+        for (int q = 0; q < D; ++q) adagrad_inplace(v[q], v[D + q], g[q], lr, eps);
+      },
+      loss, B, N, NS, D, gamma_e, gamma_r, thr_e, thr_r, drop_seed);
+}
+
 // CPU twin of uniform_draw_gpu: the same per-chunk jump-ahead, the same
 // scratch (keys in word order here, thread-interleaved on the device), and
 // a compaction over the per-block counts.

@@ -13,7 +13,11 @@ Rebuild of the reference app (reference apps/knowledge_graph_embeddings.cc):
   - the reference's two-sided objective, opt-in: subject-side negatives
     and L2 on the positive's rows (neg_samples_subject, gamma_entity,
     gamma_relation; k_kge_step_sides, reference train() and :1106).
-    Dropout is not built.
+  - dropout, opt-in (dropout_entity, dropout_relation; reference
+    do_dropout in train()): fresh masks per scored triple, a counter
+    hash of a per-step seed computed inside the step kernels
+    (k_kge_step_drop, csrc/kernels.h has the contract). Evaluation
+    never drops. ComplEx only: Rescal ignores the two fields.
   - eval: MRR / Hits@k by scoring candidate sets (reference :544-712)
   - checkpoint: WaitSync -> Barrier -> rank-0 full pull -> save
     (reference :327-401)
@@ -53,10 +57,19 @@ class ComplExConfig:
     neg_samples_subject: int = 0  # s-side negatives per positive
     gamma_entity: float = 0.0     # L2 on the positive's s and o rows
     gamma_relation: float = 0.0   # L2 on the positive's r row
+    # dropout (ComplEx): either off its default selects the drop step, which
+    # is the sides step with masked rows. Probabilities are multiples of
+    # 1/1024 after rounding, at most 1023/1024.
+    dropout_entity: float = 0.0    # on the subject and object rows
+    dropout_relation: float = 0.0  # on the relation row
 
     @property
     def sides(self) -> bool:
         return bool(self.neg_samples_subject or self.gamma_entity or self.gamma_relation)
+
+    @property
+    def dropout(self) -> bool:
+        return bool(self.dropout_entity or self.dropout_relation)
 
     @property
     def num_keys(self) -> int:
@@ -67,7 +80,22 @@ class ComplExConfig:
         return 2 * self.dim
 
 
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x: int) -> int:
+    """pcg_hash64 of the kernels (the finaliser alias_draw uses), on Python ints."""
+    x &= _M64
+    x ^= x >> 33
+    x = (x * 0xFF51AFD7ED558CCD) & _M64
+    x ^= x >> 33
+    x = (x * 0xC4CEB9FE1A85EC53) & _M64
+    return x ^ (x >> 33)
+
+
 class ComplEx(StepModel):
+    _drop_steps = 0  # drop kernels launched so far: the step counter of drop_seed
+
     # ------------------------------------------------------------ init
 
     def init_embeddings(self):
@@ -99,7 +127,7 @@ class ComplEx(StepModel):
 
     def _neg_parts(self, neg_keys, B):
         """The negative key arrays of the classic step, role by role."""
-        if not self.cfg.sides:
+        if not self._five:
             return [neg_keys]
         n_o = B * self.cfg.neg_samples
         return [neg_keys[:n_o], neg_keys[n_o:]]
@@ -109,8 +137,27 @@ class ComplEx(StepModel):
         return (cfg.neg_samples, cfg.neg_samples_subject, cfg.dim, cfg.lr, cfg.eps,
                 cfg.gamma_entity, cfg.gamma_relation)
 
+    @property
+    def _five(self) -> bool:
+        """Five key arrays per step (s | r | o | neg_o | neg_s), not four."""
+        return self.cfg.sides or self.cfg.dropout
+
+    def _drop_tail(self):
+        """The drop entries' arguments after the tensors. Every launch takes
+        drop_seed = mix64(mix64(mix64(cfg.seed) ^ rank) ^ n), n = 1, 2, ...
+        counting this model's drop launches and mix64 the kernels'
+        pcg_hash64: two runs with the same seeds draw the same masks, and
+        deferred samples take the seed of the step they run in."""
+        cfg = self.cfg
+        self._drop_steps += 1
+        seed = _mix64(_mix64(_mix64(cfg.seed) ^ self.rank) ^ self._drop_steps)
+        return (*self._sides_tail(), cfg.dropout_entity, cfg.dropout_relation, seed)
+
     def _launch(self, v, d, loss):
         cfg = self.cfg
+        if cfg.dropout:  # v, d: s | r | o | neg_o | neg_s
+            _C.kge_complex_step_drop(*v, *d, loss, *self._drop_tail())
+            return
         if cfg.sides:  # v, d: s | r | o | neg_o | neg_s
             _C.kge_complex_step_sides(*v, *d, loss, *self._sides_tail())
             return
@@ -130,7 +177,7 @@ class ComplEx(StepModel):
                                  wait_push=not async_push)
 
     def _classic_step(self, arrays):
-        if self.cfg.sides:
+        if self._five:
             triples, negs_o, negs_s = arrays
             return self.train_batch(triples, sync_loss=False, neg_keys=np.concatenate(
                 [negs_o.reshape(-1), negs_s.reshape(-1)]))
@@ -139,22 +186,26 @@ class ComplEx(StepModel):
 
     def _fused_identity_step(self, arrays):
         raw = self.server.raw
+        if self.cfg.dropout:
+            return self._fused_raw(raw.kge_step_drop_fused, arrays)
         return self._fused_raw(
             raw.kge_step_sides_fused if self.cfg.sides else raw.kge_step_fused, arrays)
 
     def _fused_general_step(self, arrays):
         raw = self.server.raw
+        if self.cfg.dropout:
+            return self._fused_raw(raw.kge_step_drop_fused_general, arrays)
         return self._fused_raw(raw.kge_step_sides_fused_general if self.cfg.sides
                                else raw.kge_step_fused_general, arrays)
 
     def _fused_raw(self, step, arrays):
         cfg = self.cfg
-        if cfg.sides:
+        if self._five:
             triples, negs_o, negs_s = arrays
             return step(*map(torch.from_numpy, self.keys_of(triples)),
                         torch.from_numpy(np.ascontiguousarray(negs_o.reshape(-1))),
                         torch.from_numpy(np.ascontiguousarray(negs_s.reshape(-1))),
-                        *self._sides_tail())
+                        *(self._drop_tail() if cfg.dropout else self._sides_tail()))
         triples, negs2 = arrays
         return step(*map(torch.from_numpy, self.keys_of(triples)),
                     torch.from_numpy(np.ascontiguousarray(negs2.reshape(-1))),
@@ -184,6 +235,10 @@ class ComplEx(StepModel):
             sid = w.prepare_sample(NN, w.current_clock(), w.current_clock() + 2)
             us = smp.pull_device(w, sid, NN, draw=False)
             w.finish_sample(sid)
+            if cfg.dropout:
+                loss, _neg = self.server.raw.kge_step_drop_fused_sampled(
+                    *map(torch.from_numpy, self.keys_of(triples)), us, *self._drop_tail())
+                return self._loss_out(loss, sync_loss)
             if cfg.sides:
                 loss, _neg = self.server.raw.kge_step_sides_fused_sampled(
                     *map(torch.from_numpy, self.keys_of(triples)), us, *self._sides_tail())
@@ -193,7 +248,7 @@ class ComplEx(StepModel):
                 us, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
             return self._loss_out(loss, sync_loss)
         negs2 = np.ascontiguousarray(self._draw_negatives(B), dtype=np.int64)
-        if cfg.sides:
+        if self._five:
             n_o = B * cfg.neg_samples
             return self._fused_step((triples, negs2[:n_o].reshape(B, cfg.neg_samples),
                                      negs2[n_o:].reshape(B, cfg.neg_samples_subject)),
@@ -441,6 +496,10 @@ def main():
                     help="L2 on the positive's entity rows (reference: 1e-3)")
     ap.add_argument("--gamma-relation", type=float, default=0.0,
                     help="L2 on the positive's relation row (reference: 1e-3)")
+    ap.add_argument("--dropout-entity", type=float, default=0.0,
+                    help="dropout on the subject and object rows (reference: --dropout_entity)")
+    ap.add_argument("--dropout-relation", type=float, default=0.0,
+                    help="dropout on the relation row (reference: --dropout_relation)")
     ap.add_argument("--triples", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--epochs", type=int, default=2)
@@ -463,7 +522,8 @@ def main():
     cfg = ComplExConfig(num_entities=a.entities, num_relations=a.relations, dim=a.dim,
                         neg_samples=a.neg, batch_size=a.batch, lr=a.lr,
                         neg_samples_subject=a.neg_samples_subject,
-                        gamma_entity=a.gamma_entity, gamma_relation=a.gamma_relation)
+                        gamma_entity=a.gamma_entity, gamma_relation=a.gamma_relation,
+                        dropout_entity=a.dropout_entity, dropout_relation=a.dropout_relation)
     model = ComplEx(cfg, server, worker)
     model.init_embeddings()
     rank = server.my_rank()

@@ -35,15 +35,18 @@ SOURCES = [
     "mfma_hip.hip",
     "ctr_hip.hip",
     "rescal_fused_hip.hip",
+    "kge_drop_hip.hip",
     "kernels_cpu.cpp",
 ]
 
-# Per-source flags. ctr_hip.hip adds float4 lanes element by element; it and
-# rescal_fused_hip.hip are built without the packed fp32 instructions.
+# Per-source flags. ctr_hip.hip adds float4 lanes element by element; it,
+# rescal_fused_hip.hip and kge_drop_hip.hip are built without the packed fp32
+# instructions.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "ctr_hip.hip": NO_PACKED_FP32,
     "rescal_fused_hip.hip": NO_PACKED_FP32,
+    "kge_drop_hip.hip": NO_PACKED_FP32,
 }
 
 MODULE = "_C"

@@ -6,9 +6,11 @@ on the device). One process measures one step:
   --step sides   N object-side + NS subject-side negatives, gammas 1e-3
   --step one     the existing step with N + NS object-side negatives
 
-Both touch 3 + N + NS rows per positive. Run them ABBA in one session on one
-box and compare by slot parity (docs/NOTES_NEXT_ROUND.md). Prints one JSON
-line; metric = ms per step."""
+Both touch 3 + N + NS rows per positive. --dropout-entity / --dropout-relation
+put the sides step's dropout variant (k_kge_step_drop_fused) in its place, so
+`--step sides` with and without them is the cost of dropout. Run the two
+sides of a comparison ABBA in one session on one box and compare by slot
+parity (docs/NOTES_NEXT_ROUND.md). Prints one JSON line; metric = ms per step."""
 import argparse
 import json
 import os
@@ -33,6 +35,8 @@ def main():
     ap.add_argument("--neg", type=int, default=8, help="object-side negatives of the sides step")
     ap.add_argument("--neg-subject", type=int, default=8)
     ap.add_argument("--gamma", type=float, default=1e-3)
+    ap.add_argument("--dropout-entity", type=float, default=0.0)
+    ap.add_argument("--dropout-relation", type=float, default=0.0)
     ap.add_argument("--batch", type=int, default=16384)
     ap.add_argument("--device", type=str, default=None)
     args = ap.parse_args()
@@ -49,7 +53,8 @@ def main():
         cfg = ComplExConfig(num_entities=args.entities, num_relations=args.relations,
                             dim=args.dim, neg_samples=args.neg, batch_size=args.batch, seed=7,
                             neg_samples_subject=args.neg_subject, gamma_entity=args.gamma,
-                            gamma_relation=args.gamma)
+                            gamma_relation=args.gamma, dropout_entity=args.dropout_entity,
+                            dropout_relation=args.dropout_relation)
     else:
         cfg = ComplExConfig(num_entities=args.entities, num_relations=args.relations,
                             dim=args.dim, neg_samples=args.neg + args.neg_subject,
@@ -104,6 +109,7 @@ def main():
         "config": {"dim": args.dim, "batch": args.batch, "entities": args.entities,
                    "neg_object": cfg.neg_samples, "neg_subject": cfg.neg_samples_subject,
                    "gamma": args.gamma if args.step == "sides" else 0.0,
+                   "dropout": [cfg.dropout_entity, cfg.dropout_relation],
                    "rows_per_positive": rows,
                    "pull_push_ops_per_s": 2 * rows * args.batch * args.steps / el},
     }), flush=True)

@@ -3535,6 +3535,51 @@ class Server {
         });
   }
 
+  // The two-sided fused RESCAL step with dropout (kernels.h,
+  // rescal_step_drop_fused_gpu): the entry above with the two dropout
+  // probabilities and the seed of the masks, and one scratch tensor of a
+  // D x D partial per tile. The masks are indexed by a sample's position among
+  // the HIT samples, in the sorted and compacted arrays the step runs on.
+  // p_e = p_r = 0 is not special-cased (kernels.h).
+  std::tuple<torch::Tensor, torch::Tensor> rescal_step_drop_fused_general(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, torch::Tensor keys_neg_o,
+      torch::Tensor keys_neg_s, int64_t N, int64_t NS, int64_t D, double lr, double eps,
+      double gamma_e, double gamma_r, double p_e, double p_r, uint64_t drop_seed) {
+    const char* name = "rescal_step_drop_fused";
+    const auto thr = check_drop(name, p_e, p_r);
+    TORCH_CHECK(N >= 0 && NS >= 0, name, ": N = ", N, " and NS = ", NS, " must be >= 0");
+    TORCH_CHECK(std::isfinite(gamma_e) && gamma_e >= 0 && std::isfinite(gamma_r) && gamma_r >= 0,
+                name, ": gamma_e = ", gamma_e, " and gamma_r = ", gamma_r,
+                " must be finite and >= 0");
+    check_rescal_fused(name,
+                       {{&keys_s, 1, "keys_s"}, {&keys_o, 1, "keys_o"}, {&keys_neg_o, N, "keys_neg_o"},
+                        {&keys_neg_s, NS, "keys_neg_s"}},
+                       keys_r, D, RESCAL_DROP_MAX_DIM);
+    return step_fused_general(
+        name, {{&keys_s, 1}, {&keys_r, 1}, {&keys_o, 1}, {&keys_neg_o, N}, {&keys_neg_s, NS}},
+        [&](const FusedResolve& res, float* loss) {
+          const int Bh = (int)res.b_hit;
+          const RescalGroups gr = rescal_groups(res.offs[1], Bh);
+          if (!dev_.is_cuda()) {
+            std::lock_guard<std::mutex> vg(cpu_val_mu_);
+            rescal_step_drop_fused_offs_cpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3],
+                                            res.ptr[4], gr.offs_rg.data(), gr.starts.data(), loss,
+                                            Bh, gr.G, (int)N, (int)NS, (int)D, (float)lr,
+                                            (float)eps, (float)gamma_e, (float)gamma_r, thr.first,
+                                            thr.second, drop_seed);
+            return;
+          }
+          const RescalBlob bl = rescal_blob(name, res, gr);
+          auto scratch = torch::empty({(int64_t)bl.n_tiles * D * D},
+                                      torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+          rescal_step_drop_fused_gpu(slab_.data, res.ptr[0], res.ptr[2], res.ptr[3], res.ptr[4],
+                                     bl.offs_rg, bl.starts, bl.tiles, bl.n_tiles,
+                                     scratch.data_ptr<float>(), loss, Bh, gr.G, (int)N, (int)NS,
+                                     (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r,
+                                     thr.first, thr.second, drop_seed, current_stream(dev_));
+        });
+  }
+
   // ---- pieces the two fused RESCAL entries share
 
   // One entity key role: the array, its keys per sample, and the name the
@@ -3548,11 +3593,11 @@ class Server {
   // Argument checks: D, the key budget, every role's count and row length,
   // and keys_r made of runs of distinct relations.
   void check_rescal_fused(const char* name, std::initializer_list<RescalRole> ents,
-                          const torch::Tensor& keys_r, int64_t D) {
+                          const torch::Tensor& keys_r, int64_t D,
+                          int64_t max_dim = RESCAL_FUSED_MAX_DIM) {
     TORCH_CHECK(D >= 4 && D % 4 == 0, name, ": D = ", D, " must be a positive multiple of 4");
     if (dev_.is_cuda())
-      TORCH_CHECK(D <= RESCAL_FUSED_MAX_DIM, name, ": D = ", D, " exceeds the GPU kernels' limit of ",
-                  RESCAL_FUSED_MAX_DIM);
+      TORCH_CHECK(D <= max_dim, name, ": D = ", D, " exceeds the GPU kernels' limit of ", max_dim);
     const int64_t B = ents.begin()->keys->numel();
     std::vector<RescalRole> roles(ents);
     roles.push_back({&keys_r, 1, "keys_r"});
@@ -4725,6 +4770,67 @@ torch::Tensor rescal_step_sides_grouped(torch::Tensor s, torch::Tensor rm, torch
   return loss;
 }
 
+// RESCAL sides step with dropout (kernels.h, rescal_step_drop): the tensors of
+// rescal_step_sides_grouped, any D >= 1, on CPU or GPU tensors. Groups of one
+// positive (starts = 0..B) give the per-triple step. No group may be empty:
+// a group's drl row is written by the group's first tile.
+torch::Tensor rescal_step_drop(torch::Tensor s, torch::Tensor rm, torch::Tensor o,
+                               torch::Tensor neg_o, torch::Tensor neg_s, torch::Tensor ds,
+                               torch::Tensor drl, torch::Tensor do_, torch::Tensor dneg_o,
+                               torch::Tensor dneg_s, torch::Tensor starts, int64_t N, int64_t NS,
+                               int64_t D, double lr, double eps, double gamma_e, double gamma_r,
+                               double p_e, double p_r, uint64_t drop_seed) {
+  const char* name = "rescal_step_drop";
+  const auto thr = check_drop(name, p_e, p_r);
+  TORCH_CHECK(D >= 1 && D <= 8192, name, ": D = ", D, " must be in [1, 8192]");
+  TORCH_CHECK(starts.scalar_type() == torch::kInt32 && starts.device().is_cpu() &&
+                  starts.is_contiguous() && starts.numel() >= 1,
+              name, ": starts must be a contiguous int32 CPU tensor of G + 1 offsets");
+  const int64_t G = starts.numel() - 1;
+  const int32_t* sp = starts.data_ptr<int32_t>();
+  TORCH_CHECK(sp[0] == 0, name, ": starts[0] must be 0");
+  for (int64_t g = 0; g < G; ++g)
+    TORCH_CHECK(sp[g + 1] > sp[g], name, ": starts must increase (no group may be empty)");
+  const int64_t B = sp[G];
+  check_rescal_sides(name, s, o, neg_o, neg_s, ds, do_, dneg_o, dneg_s, {&rm, &drl}, B, N, NS,
+                     D, gamma_e, gamma_r);
+  for (auto* t : {&rm, &drl})
+    TORCH_CHECK(t->numel() == G * 2 * D * D, name, ": rm and drl must be [G][2*D*D]");
+  if (s.is_cuda()) {
+    TORCH_CHECK(hip_available(), name, ": CUDA tensor but no HIP device");
+    TORCH_CHECK(D <= RESCAL_DROP_MAX_DIM, name, ": D = ", D,
+                " exceeds the GPU kernels' limit of ", (int)RESCAL_DROP_MAX_DIM);
+  }
+  auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(s.device()));
+  if (B == 0) return loss;
+  if (!s.is_cuda()) {
+    rescal_step_drop_cpu(cfp(s), cfp(rm), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(drl), fp(do_),
+                         fp(dneg_o), fp(dneg_s), sp, fp(loss), (int)B, (int)G, (int)N, (int)NS,
+                         (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r, thr.first,
+                         thr.second, drop_seed);
+    return loss;
+  }
+  // starts | tiles go up as one int32 tensor
+  std::vector<int32_t> meta(sp, sp + G + 1);
+  for (int64_t g = 0; g < G; ++g)
+    for (int32_t m0 = 0; m0 < sp[g + 1] - sp[g]; m0 += 16) {
+      meta.push_back((int32_t)g);
+      meta.push_back(m0);
+    }
+  const int64_t n_tiles = ((int64_t)meta.size() - (G + 1)) / 2;
+  auto meta_d = torch::from_blob(meta.data(), {(int64_t)meta.size()}, torch::kInt32)
+                    .to(s.device());
+  auto scratch = torch::empty({n_tiles * D * D},
+                              torch::TensorOptions().dtype(torch::kFloat32).device(s.device()));
+  const int32_t* md = meta_d.data_ptr<int32_t>();
+  rescal_step_drop_gpu(cfp(s), cfp(rm), cfp(o), cfp(neg_o), cfp(neg_s), fp(ds), fp(drl), fp(do_),
+                       fp(dneg_o), fp(dneg_s), md, md + G + 1, (int)n_tiles,
+                       scratch.data_ptr<float>(), fp(loss), (int)B, (int)G, (int)N, (int)NS,
+                       (int)D, (float)lr, (float)eps, (float)gamma_e, (float)gamma_r, thr.first,
+                       thr.second, drop_seed, current_stream(s.device()));
+  return loss;
+}
+
 void w2v_sgns_step(torch::Tensor ctr, torch::Tensor ctx, torch::Tensor neg, torch::Tensor dctr,
                    torch::Tensor dctx, torch::Tensor dneg, torch::Tensor loss, int64_t N,
                    int64_t D, double lr, double eps) {
@@ -4995,6 +5101,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rescal_step", &rescal_step, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_grouped", &rescal_step_grouped, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_sides", &rescal_step_sides, py::call_guard<py::gil_scoped_release>());
+  m.def("rescal_step_drop", &rescal_step_drop, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_sides_grouped", &rescal_step_sides_grouped,
         py::call_guard<py::gil_scoped_release>());
   m.def("kge_complex_score", &kge_complex_score, py::call_guard<py::gil_scoped_release>());
@@ -5029,6 +5136,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("CTR_SEG_CHUNK") = (int)CTR_SEG_CHUNK;
   m.attr("CTR_MAX_DIM") = (int)CTR_MAX_DIM;
   m.attr("RESCAL_FUSED_MAX_DIM") = (int)RESCAL_FUSED_MAX_DIM;
+  m.attr("RESCAL_DROP_MAX_DIM") = (int)RESCAL_DROP_MAX_DIM;
   py::class_<CtrBatch, std::shared_ptr<CtrBatch>>(m, "CtrBatch")
       .def("__len__", [](const CtrBatch& b) { return b.n; });
   py::class_<Server>(m, "Server")
@@ -5089,6 +5197,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("kge_step_drop_fused_general", &Server::kge_step_drop_fused_general,
            py::call_guard<py::gil_scoped_release>())
       .def("rescal_step_sides_fused_general", &Server::rescal_step_sides_fused_general,
+           py::call_guard<py::gil_scoped_release>())
+      .def("rescal_step_drop_fused_general", &Server::rescal_step_drop_fused_general,
            py::call_guard<py::gil_scoped_release>())
       .def("rescal_step_fused_general", &Server::rescal_step_fused_general,
            py::call_guard<py::gil_scoped_release>())

@@ -446,6 +446,99 @@ void rescal_step_sides_fused_offs_cpu(float* slab, const int64_t* offs_s, const 
                                       int B, int G, int N, int NS, int D, float lr, float eps,
                                       float gamma_e, float gamma_r);
 
+// RESCAL sides step WITH DROPOUT (rescal_drop_hip.hip; reference do_dropout in
+// train(), which both scorers share). One sample is the sides step's: a
+// positive (s, R, o), N object-side negatives (s, R, o'_j), NS subject-side
+// negatives (s'_j, R, o). Its scored triples are numbered
+//   t = 0             the positive
+//   t = 1 .. N        the object-side negatives
+//   t = N+1 .. N+NS   the subject-side negatives,        T = 1 + N + NS
+// and every scored triple draws fresh masks for its three rows, over the
+// embedding floats (D of an entity row, D*D of R), never over the accumulators:
+//   psi_t = (m_s ⊙ s_t)^T (M_t ⊙ R) (m_o ⊙ o_t),  mask values 0 or scale,
+// with drop_threshold, drop_scale and the 10-bit fields of the ComplEx drop
+// step above: thr_e = lround(p_e * 1024) for the entity masks, thr_r likewise
+// from p_r, a component kept iff its field >= thr, scale = 1024 / (1024 - thr).
+// Objective and gradient (the choices docs/PARITY.md 2.3 records for ComplEx):
+//   - psi is taken on the masked rows; loss[b] sums the T logistic terms
+//     (softplus1pf on the GPU) and leaves the regulariser's value out;
+//   - the gradient is the true gradient through the masks: a dropped
+//     component gets an exact 0 from that triple, a kept one `scale` times the
+//     gradient with respect to the masked value;
+//   - gamma_e and gamma_r act on the STORED rows of the positive;
+//   - every entity row occurrence gets ONE AdaGrad update of its summed
+//     gradient (s: t = 0..N, o: t = 0 and t > N, o'_j and s'_j their own term);
+//   - R gets the AdaGrad transform of the group-summed gradient plus
+//     gamma_r * Bg * R, as in rescal_step_sides_grouped. With groups of one
+//     positive (starts = 0..B) that is the per-triple semantics.
+// The gradient of R is sum_t g_t * M_t ⊙ (s~_t o~_t^T): with a fresh M_t per
+// triple nothing factors through u = R^T s or v = R o, so a triple costs about
+// 3 D^2 whatever one does.
+// Mask index, everything in 64 bits: q = b * T + t, b the position in THIS
+// call's arrays (the sorted order; on the general path the sorted and
+// compacted one).
+//   entity masks    for k < D: h = pcg_hash64(drop_seed ^ (q*D + k) * 0x9e3779b97f4a7c15)
+//                   field 0 (bits 0..9) is the subject ROLE of the triple (s or
+//                   s'_j), field 1 (bits 10..19) the object role (o or o'_j);
+//                   kept iff field >= thr_e
+//   relation masks  element e = i*D + j of R (row-major, psi = sum s_i R_ij o_j),
+//                   Q = (D*D + 3) / 4:
+//                   h = pcg_hash64(~drop_seed ^ (q*Q + (e >> 2)) * 0x9e3779b97f4a7c15)
+//                   field e & 3, kept iff field >= thr_r: one hash serves four
+//                   consecutive floats of R, one 16-byte load
+// With thr_r == 0 no relation hash is taken (every element kept, scale 1), and
+// likewise thr_e and the entity hash. The entry points do NOT special-case
+// thr_e == thr_r == 0: the drop kernels then run with every component kept, and
+// the result is within tolerance of the sides step, not bit-equal to it.
+//
+// Layout: samples sorted by relation, group g = samples [starts[g],
+// starts[g+1]), no group empty; tiles [n_tiles][2] = (g, m0) for every run of
+// 16 samples of every group, as for rescal_step_fused_gpu. Two launches:
+//   1  one workgroup per tile: R_g staged in LDS once, then the tile's
+//      positives and their T triples one after the other. Entity rows are
+//      finished here. The tile's share of dR is summed in registers across
+//      all its triples and stored once, to scratch[tile][D*D].
+//   2  per group: the tile partials added in tile order, plus gamma_r*Bg*R,
+//      then R's AdaGrad update.
+// No atomic touches a partial, so on distinct keys the step is bit-reproducible.
+// The classic variant reads pulled rows ([n][2D], rm [G][2 D*D]) and writes
+// push deltas of the same shapes, any 1 <= D <= RESCAL_DROP_MAX_DIM. The fused
+// variant works on slab + offs[i] with the fused steps' contract given above
+// rescal_step_fused_gpu (atomicAdd of the delta and of g^2, the accumulator
+// read before it with a plain load; R updated by launch 2) and also needs
+// D % 4 == 0. starts and tiles are DEVICE pointers for the GPU entries, starts
+// a host pointer for the CPU twins; scratch holds n_tiles * D*D floats,
+// contents irrelevant. RESCAL_DROP_MAX_DIM is what R, nine D-vectors and the
+// register-held dR share of a workgroup fit (160 KB of LDS, no scratch memory);
+// callers check it. The CPU twins are serial; the fused one works in place in
+// the manner of rescal_step_sides_fused_offs_cpu (copies of s and o, the
+// negatives updated as they are scored, R at the end of its group).
+constexpr int RESCAL_DROP_MAX_DIM = 196;
+void rescal_step_drop_gpu(const float* s, const float* rm, const float* o, const float* neg_o,
+                          const float* neg_s, float* ds, float* drl, float* do_, float* dneg_o,
+                          float* dneg_s, const int32_t* starts, const int32_t* tiles, int n_tiles,
+                          float* scratch, float* loss, int B, int G, int N, int NS, int D,
+                          float lr, float eps, float gamma_e, float gamma_r, int thr_e, int thr_r,
+                          uint64_t drop_seed, void* stream);
+void rescal_step_drop_cpu(const float* s, const float* rm, const float* o, const float* neg_o,
+                          const float* neg_s, float* ds, float* drl, float* do_, float* dneg_o,
+                          float* dneg_s, const int32_t* starts, float* loss, int B, int G, int N,
+                          int NS, int D, float lr, float eps, float gamma_e, float gamma_r,
+                          int thr_e, int thr_r, uint64_t drop_seed);
+void rescal_step_drop_fused_gpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                const int64_t* offs_rg, const int32_t* starts,
+                                const int32_t* tiles, int n_tiles, float* scratch, float* loss,
+                                int B, int G, int N, int NS, int D, float lr, float eps,
+                                float gamma_e, float gamma_r, int thr_e, int thr_r,
+                                uint64_t drop_seed, void* stream);
+void rescal_step_drop_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                     const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                     const int64_t* offs_rg, const int32_t* starts, float* loss,
+                                     int B, int G, int N, int NS, int D, float lr, float eps,
+                                     float gamma_e, float gamma_r, int thr_e, int thr_r,
+                                     uint64_t drop_seed);
+
 // word2vec SGNS step: per center/context pair with N negatives.
 //  ctr:  [B][2D] center (syn0) rows;  ctx: [B][2D] context (syn1) rows
 //  neg:  [B*N][2D] negative (syn1) rows

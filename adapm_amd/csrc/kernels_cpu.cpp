@@ -726,6 +726,142 @@ void kge_complex_step_drop_fused_offs_cpu(float* slab, const int64_t* offs_s,
       loss, B, N, NS, D, gamma_e, gamma_r, thr_e, thr_r, drop_seed);
 }
 
+// ---- RESCAL sides step with dropout (kernels.h, rescal_step_drop)
+
+// One group after the other, and within a group one sample after the other:
+// copies of s and o, the T triples (a negative updated as soon as it is
+// scored), s and o, and at the end of the group R from the summed gradient.
+// row(role, i) is the i-th row [emb(D) | acc(D)] of role s, o, neg_o, neg_s =
+// 0..3 and upd(role, i, g) applies the AdaGrad update of gradient g[D] to it;
+// rel(g) is R_g [D*D | D*D] and updr(g, dR, gr) updates it with dR + gr * R.
+template <typename Row, typename Upd, typename Rel, typename UpdR>
+static void rescal_drop_serial(Row row, Upd upd, Rel rel, UpdR updr, const int32_t* starts,
+                               float* loss, int B, int G, int N, int NS, int D, float gamma_e,
+                               float gamma_r, int thr_e, int thr_r, uint64_t seed) {
+  const int64_t dd = (int64_t)D * D;
+  const uint64_t T = 1 + (uint64_t)N + (uint64_t)NS, Q = (uint64_t)((dd + 3) >> 2);
+  const float sc_e = drop_scale(thr_e), sc_r = drop_scale(thr_r);
+  std::vector<float> sv(D), ov(D), xm(D), ym(D), ms(D), mo(D), gs(D), go(D), gx(D), gy(D), mr(dd);
+  std::vector<double> a(D), bs(D), dR(dd);
+  for (int g = 0; g < G; ++g) {
+    const float* R = rel(g);
+    std::fill(dR.begin(), dR.end(), 0.0);
+    const int b1 = std::min<int>(starts[g + 1], B);
+    for (int b = starts[g]; b < b1; ++b) {
+      std::copy(row(0, b), row(0, b) + D, sv.begin());
+      std::copy(row(1, b), row(1, b) + D, ov.begin());
+      std::fill(gs.begin(), gs.end(), 0.f);
+      std::fill(go.begin(), go.end(), 0.f);
+      float lsum = 0.f;
+      for (int t = 0; t < (int)T; ++t) {
+        const uint64_t q = (uint64_t)b * T + (uint64_t)t;
+        const bool oneg = t >= 1 && t <= N, sneg = t > N;
+        const int64_t jn = oneg ? (int64_t)b * N + (t - 1) : (int64_t)b * NS + (t - N - 1);
+        const float* x = sneg ? row(3, jn) : sv.data();
+        const float* y = oneg ? row(2, jn) : ov.data();
+        for (int k = 0; k < D; ++k) {
+          ms[k] = mo[k] = 1.f;
+          if (thr_e) {
+            const uint64_t h = pcg_hash64_c(
+                seed ^ (q * (uint64_t)D + (uint64_t)k) * 0x9e3779b97f4a7c15ULL);
+            ms[k] = ((uint32_t)h & (DROP_ONE - 1)) >= (uint32_t)thr_e ? sc_e : 0.f;
+            mo[k] = ((uint32_t)(h >> DROP_FIELD_BITS) & (DROP_ONE - 1)) >= (uint32_t)thr_e ? sc_e
+                                                                                          : 0.f;
+          }
+          xm[k] = ms[k] * x[k];
+          ym[k] = mo[k] * y[k];
+        }
+        uint64_t h = 0;
+        for (int64_t e = 0; e < dd; ++e) {
+          mr[e] = 1.f;
+          if (!thr_r) continue;
+          if ((e & 3) == 0) h = pcg_hash64_c(~seed ^ (q * Q + (uint64_t)(e >> 2)) * 0x9e3779b97f4a7c15ULL);
+          const uint32_t f = (uint32_t)(h >> (DROP_FIELD_BITS * (e & 3))) & (DROP_ONE - 1);
+          mr[e] = f >= (uint32_t)thr_r ? sc_r : 0.f;
+        }
+        std::fill(bs.begin(), bs.end(), 0.0);
+        double psi = 0.0;
+        for (int i = 0; i < D; ++i) {
+          double ai = 0.0;
+          for (int j = 0; j < D; ++j) {
+            const float rm = mr[(int64_t)i * D + j] * R[(int64_t)i * D + j];
+            ai += (double)rm * ym[j];
+            bs[j] += (double)rm * xm[i];
+          }
+          a[i] = ai;
+          psi += ai * xm[i];
+        }
+        const float yl = t == 0 ? 1.f : -1.f;
+        const float c = -yl * sigmoidf_(-yl * (float)psi);
+        lsum += softplusf_(-yl * (float)psi);
+        for (int i = 0; i < D; ++i) {
+          gx[i] = c * ms[i] * (float)a[i];
+          gy[i] = c * mo[i] * (float)bs[i];
+          for (int j = 0; j < D; ++j)
+            dR[(int64_t)i * D + j] += (double)(c * mr[(int64_t)i * D + j]) * xm[i] * ym[j];
+        }
+        if (sneg) upd(3, jn, gx.data());
+        else for (int k = 0; k < D; ++k) gs[k] += gx[k];
+        if (oneg) upd(2, jn, gy.data());
+        else for (int k = 0; k < D; ++k) go[k] += gy[k];
+      }
+      for (int k = 0; k < D; ++k) gs[k] += gamma_e * sv[k], go[k] += gamma_e * ov[k];
+      upd(0, b, gs.data());
+      upd(1, b, go.data());
+      loss[b] = lsum;
+    }
+    updr(g, dR.data(), gamma_r * (float)(b1 - starts[g]));
+  }
+}
+
+void rescal_step_drop_cpu(const float* s, const float* rm, const float* o, const float* neg_o,
+                          const float* neg_s, float* ds, float* drl, float* do_, float* dneg_o,
+                          float* dneg_s, const int32_t* starts, float* loss, int B, int G, int N,
+                          int NS, int D, float lr, float eps, float gamma_e, float gamma_r,
+                          int thr_e, int thr_r, uint64_t drop_seed) {
+  const float* in[4] = {s, o, neg_o, neg_s};
+  float* out[4] = {ds, do_, dneg_o, dneg_s};
+  const int64_t rowlen = 2 * (int64_t)D, dd = (int64_t)D * D;
+  rescal_drop_serial(
+      [&](int role, int64_t i) { return in[role] + i * rowlen; },
+      [&](int role, int64_t i, const float* g) {
+        const float* v = in[role] + i * rowlen;
+        float* d = out[role] + i * rowlen;
+        for (int q = 0; q < D; ++q) write_delta_(&d[q], &d[D + q], g[q], v[D + q], lr, eps);
+      },
+      [&](int g) { return rm + (int64_t)g * 2 * dd; },
+      [&](int g, const double* dR, float gr) {
+        const float* R = rm + (int64_t)g * 2 * dd;
+        float* d = drl + (int64_t)g * 2 * dd;
+        for (int64_t e = 0; e < dd; ++e)
+          write_delta_(&d[e], &d[dd + e], (float)dR[e] + gr * R[e], R[dd + e], lr, eps);
+      },
+      starts, loss, B, G, N, NS, D, gamma_e, gamma_r, thr_e, thr_r, drop_seed);
+}
+
+void rescal_step_drop_fused_offs_cpu(float* slab, const int64_t* offs_s, const int64_t* offs_o,
+                                     const int64_t* offs_neg_o, const int64_t* offs_neg_s,
+                                     const int64_t* offs_rg, const int32_t* starts, float* loss,
+                                     int B, int G, int N, int NS, int D, float lr, float eps,
+                                     float gamma_e, float gamma_r, int thr_e, int thr_r,
+                                     uint64_t drop_seed) {
+  const int64_t* offs[4] = {offs_s, offs_o, offs_neg_o, offs_neg_s};
+  const int64_t dd = (int64_t)D * D;
+  rescal_drop_serial(
+      [&](int role, int64_t i) { return slab + offs[role][i]; },
+      [&](int role, int64_t i, const float* g) {
+        float* v = slab + offs[role][i];
+        for (int q = 0; q < D; ++q) adagrad_inplace(v[q], v[D + q], g[q], lr, eps);
+      },
+      [&](int g) { return slab + offs_rg[g]; },
+      [&](int g, const double* dR, float gr) {
+        float* R = slab + offs_rg[g];
+        for (int64_t e = 0; e < dd; ++e)
+          adagrad_inplace(R[e], R[dd + e], (float)dR[e] + gr * R[e], lr, eps);
+      },
+      starts, loss, B, G, N, NS, D, gamma_e, gamma_r, thr_e, thr_r, drop_seed);
+}
+
 // CPU twin of uniform_draw_gpu: the same per-chunk jump-ahead, the same
 // scratch (keys in word order here, thread-interleaved on the device), and
 // a compaction over the per-block counts.

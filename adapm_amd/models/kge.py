@@ -16,8 +16,8 @@ Rebuild of the reference app (reference apps/knowledge_graph_embeddings.cc):
   - dropout, opt-in (dropout_entity, dropout_relation; reference
     do_dropout in train()): fresh masks per scored triple, a counter
     hash of a per-step seed computed inside the step kernels
-    (k_kge_step_drop, csrc/kernels.h has the contract). Evaluation
-    never drops. ComplEx only: Rescal ignores the two fields.
+    (k_kge_step_drop, and k_rescal_drop for Rescal; csrc/kernels.h has
+    both contracts). Evaluation never drops.
   - eval: MRR / Hits@k by scoring candidate sets (reference :544-712)
   - checkpoint: WaitSync -> Barrier -> rank-0 full pull -> save
     (reference :327-401)
@@ -57,7 +57,7 @@ class ComplExConfig:
     neg_samples_subject: int = 0  # s-side negatives per positive
     gamma_entity: float = 0.0     # L2 on the positive's s and o rows
     gamma_relation: float = 0.0   # L2 on the positive's r row
-    # dropout (ComplEx): either off its default selects the drop step, which
+    # dropout (both scorers): either off its default selects the drop step, which
     # is the sides step with masked rows. Probabilities are multiples of
     # 1/1024 after rounding, at most 1023/1024.
     dropout_entity: float = 0.0    # on the subject and object rows
@@ -91,6 +91,19 @@ def _mix64(x: int) -> int:
     x ^= x >> 33
     x = (x * 0xC4CEB9FE1A85EC53) & _M64
     return x ^ (x >> 33)
+
+
+def _drop_tail(model):
+    """What the drop entries of both scorers take after the sides tail: the
+    two probabilities and this launch's seed. Every launch takes
+    drop_seed = mix64(mix64(mix64(cfg.seed) ^ rank) ^ n), n = 1, 2, ...
+    counting the model's drop launches and mix64 the kernels' pcg_hash64:
+    two runs with the same seeds draw the same masks, and deferred samples
+    take the seed of the step they run in."""
+    cfg = model.cfg
+    model._drop_steps += 1
+    seed = _mix64(_mix64(_mix64(cfg.seed) ^ model.rank) ^ model._drop_steps)
+    return cfg.dropout_entity, cfg.dropout_relation, seed
 
 
 class ComplEx(StepModel):
@@ -143,15 +156,9 @@ class ComplEx(StepModel):
         return self.cfg.sides or self.cfg.dropout
 
     def _drop_tail(self):
-        """The drop entries' arguments after the tensors. Every launch takes
-        drop_seed = mix64(mix64(mix64(cfg.seed) ^ rank) ^ n), n = 1, 2, ...
-        counting this model's drop launches and mix64 the kernels'
-        pcg_hash64: two runs with the same seeds draw the same masks, and
-        deferred samples take the seed of the step they run in."""
-        cfg = self.cfg
-        self._drop_steps += 1
-        seed = _mix64(_mix64(_mix64(cfg.seed) ^ self.rank) ^ self._drop_steps)
-        return (*self._sides_tail(), cfg.dropout_entity, cfg.dropout_relation, seed)
+        """The drop entries' arguments after the tensors (_drop_tail above
+        has the seed)."""
+        return (*self._sides_tail(), *_drop_tail(self))
 
     def _launch(self, v, d, loss):
         cfg = self.cfg
@@ -572,7 +579,12 @@ class Rescal(StepModel):
     objective of ComplExConfig (neg_samples_subject, gamma_entity,
     gamma_relation) selects rescal_step_sides / rescal_step_sides_grouped.
     train_batch_fused is the opt-in slab-direct step of the one-sided
-    objective and, with fuse_sides=True, of the two-sided one."""
+    objective and, with fuse_sides=True, of the two-sided one. With
+    cfg.dropout (dropout_entity, dropout_relation) every step is the drop
+    step, rescal_step_drop / Server.rescal_step_drop_fused_general: fresh
+    masks per scored triple, seeded per launch as ComplEx seeds them."""
+
+    _drop_steps = 0  # drop launches so far: the step counter of drop_seed
 
     @staticmethod
     def value_lengths(num_entities, num_relations, dim):
@@ -638,8 +650,8 @@ class Rescal(StepModel):
         accumulator snapshot).
 
         With cfg.sides (neg_samples_subject, gamma_entity or
-        gamma_relation off its default) the step is the two-sided one,
-        _train_batch_sides. neg_keys names the negatives, sample by
+        gamma_relation off its default) or cfg.dropout the step is the
+        two-sided one, _train_batch_sides. neg_keys names the negatives, sample by
         sample in the order of `triples` as given."""
         cfg = self.cfg
         w = self.worker
@@ -654,7 +666,7 @@ class Rescal(StepModel):
         s_keys = triples[:, 0].astype(np.int64)
         r_keys = (cfg.num_entities + triples[:, 1]).astype(np.int64)
         o_keys = triples[:, 2].astype(np.int64)
-        if cfg.sides:
+        if cfg.sides or cfg.dropout:
             return self._train_batch_sides(s_keys, r_keys, o_keys, order, neg_keys, sync_loss)
         if neg_keys is None:
             neg_keys = self._negatives(B * cfg.neg_samples, cfg.num_entities)
@@ -708,18 +720,26 @@ class Rescal(StepModel):
         not local go through train_batch, deferred by one step first
         (StepModel._fused_step). neg_keys as in train_batch: with
         cfg.sides the first B * neg_samples keys corrupt the object and
-        the rest the subject."""
+        the rest the subject. With cfg.dropout the step is the fused drop
+        step whatever fuse_sides says (classic off the GPU and for a dim
+        that is no multiple of 4; a dim above _C.RESCAL_DROP_MAX_DIM is
+        refused on the GPU by either)."""
         cfg = self.cfg
+        if cfg.dropout:
+            if (self.dev.type != "cuda" and not force_general) or cfg.dim % 4:
+                return self.train_batch(triples, sync_loss=sync_loss, neg_keys=neg_keys)
+            fuse_sides = True
         if ((cfg.sides and not fuse_sides) or (self.dev.type != "cuda" and not force_general)
                 or cfg.dim % 4 or cfg.dim > _C.RESCAL_FUSED_MAX_DIM):
             return self.train_batch(triples, sync_loss=sync_loss, neg_keys=neg_keys)
         B, N = len(triples), cfg.neg_samples
-        NS = cfg.neg_samples_subject if cfg.sides else 0
+        five = cfg.sides or cfg.dropout  # a second array of negatives, maybe empty
+        NS = cfg.neg_samples_subject if five else 0
         if neg_keys is None:
             neg_keys = self._negatives(B * (N + NS), cfg.num_entities)
         neg_keys = np.ascontiguousarray(neg_keys, dtype=np.int64)
         arrays = (triples, neg_keys[:B * N].reshape(B, N))
-        if cfg.sides:
+        if five:
             arrays += (neg_keys[B * N:].reshape(B, NS),)
         return self._fused_step(arrays, sync_loss, force_general)
 
@@ -738,7 +758,11 @@ class Rescal(StepModel):
         keys = (t[:, 0], cfg.num_entities + t[:, 1], t[:, 2]) + tuple(
             n[order].reshape(-1) for n in arrays[1:])
         keys = [torch.from_numpy(np.ascontiguousarray(k, dtype=np.int64)) for k in keys]
-        if len(arrays) == 3:
+        if cfg.dropout:
+            loss, missed = self.server.raw.rescal_step_drop_fused_general(
+                *keys, cfg.neg_samples, cfg.neg_samples_subject, cfg.dim, cfg.lr, cfg.eps,
+                cfg.gamma_entity, cfg.gamma_relation, *_drop_tail(self))
+        elif len(arrays) == 3:
             loss, missed = self.server.raw.rescal_step_sides_fused_general(
                 *keys, cfg.neg_samples, cfg.neg_samples_subject, cfg.dim, cfg.lr, cfg.eps,
                 cfg.gamma_entity, cfg.gamma_relation)
@@ -767,7 +791,9 @@ class Rescal(StepModel):
         B * neg_samples corrupt the object and the rest the subject; a fifth
         pull and push for the subject-side negatives; gamma * E on the
         positive's rows inside the kernels (rescal_step_sides, and
-        rescal_step_sides_grouped when `order` is the grouped sort)."""
+        rescal_step_sides_grouped when `order` is the grouped sort). With
+        cfg.dropout the kernel is rescal_step_drop, over the groups of the
+        sort or over groups of one positive."""
         cfg = self.cfg
         w = self.worker
         B, D, N, NS = len(s_keys), cfg.dim, cfg.neg_samples, cfg.neg_samples_subject
@@ -795,7 +821,12 @@ class Rescal(StepModel):
             if len(kt):  # a side without negatives has nothing to pull or push
                 w.wait(w.pull(kt, vt, async_=True))
         deltas = [torch.empty_like(vt) for _, vt in pulls]
-        if order is not None:
+        if cfg.dropout:
+            if order is None:
+                starts = np.arange(B + 1, dtype=np.int32)
+            loss = _C.rescal_step_drop(s_v, r_v, o_v, no_v, ns_v, *deltas,
+                                       torch.from_numpy(starts), *tail, *_drop_tail(self))
+        elif order is not None:
             loss = _C.rescal_step_sides_grouped(s_v, r_v, o_v, no_v, ns_v, *deltas,
                                                 torch.from_numpy(starts), *tail)
         else:

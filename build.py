@@ -36,17 +36,20 @@ SOURCES = [
     "ctr_hip.hip",
     "rescal_fused_hip.hip",
     "kge_drop_hip.hip",
+    "rescal_drop_hip.hip",
     "kernels_cpu.cpp",
 ]
 
 # Per-source flags. ctr_hip.hip adds float4 lanes element by element; it,
-# rescal_fused_hip.hip and kge_drop_hip.hip are built without the packed fp32
+# rescal_fused_hip.hip, kge_drop_hip.hip and rescal_drop_hip.hip (float4
+# column sums, element by element) are built without the packed fp32
 # instructions.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "ctr_hip.hip": NO_PACKED_FP32,
     "rescal_fused_hip.hip": NO_PACKED_FP32,
     "kge_drop_hip.hip": NO_PACKED_FP32,
+    "rescal_drop_hip.hip": NO_PACKED_FP32,
 }
 
 MODULE = "_C"

@@ -15,6 +15,10 @@ select the two-sided objective: the F runs are the two-sided fused step
 (train_batch_fused(fuse_sides=True)), the C runs the two-sided classic step
 (ten launches around five pulls and five pushes).
 
+--dropout-entity or --dropout-relation off their defaults select the drop step
+on both paths (rescal_drop_hip.hip: two launches, fused or between five pulls
+and five pushes); compare two invocations to see what dropout costs.
+
 Run on a GPU box:  python scripts/bench_rescal_fused.py [--dim 128] [--batch 2048]
 """
 import argparse
@@ -40,6 +44,8 @@ def main():
     ap.add_argument("--neg-samples-subject", type=int, default=0)
     ap.add_argument("--gamma-entity", type=float, default=0.0)
     ap.add_argument("--gamma-relation", type=float, default=0.0)
+    ap.add_argument("--dropout-entity", type=float, default=0.0)
+    ap.add_argument("--dropout-relation", type=float, default=0.0)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--order", type=str, default="FCCFFCCF",
@@ -54,7 +60,8 @@ def main():
     NS = args.neg_samples_subject
     cfg = ComplExConfig(num_entities=E, num_relations=R, dim=D, neg_samples=N, batch_size=B,
                         neg_samples_subject=NS, gamma_entity=args.gamma_entity,
-                        gamma_relation=args.gamma_relation)
+                        gamma_relation=args.gamma_relation, dropout_entity=args.dropout_entity,
+                        dropout_relation=args.dropout_relation)
     adapm_amd.setup(num_keys=E + R, num_threads=1, device="cuda:0")
     server = adapm_amd.Server(torch.from_numpy(Rescal.value_lengths(E, R, D)))
     worker = adapm_amd.Worker(0, server)
@@ -93,7 +100,8 @@ def main():
     print(f"median: classic {med['classic']:.3f} ms, fused {med['fused']:.3f} ms, "
           f"classic / fused = {med['classic'] / med['fused']:.2f}x "
           f"(E={E}, R={R}, D={D}, B={B}, N={N}, NS={NS}, gamma_e={args.gamma_entity:g}, "
-          f"gamma_r={args.gamma_relation:g})")
+          f"gamma_r={args.gamma_relation:g}, p_e={args.dropout_entity:g}, "
+          f"p_r={args.dropout_relation:g})")
     print(json.dumps({"metric": "rescal_step_ms", "classic_ms": ms["classic"],
                       "fused_ms": ms["fused"], "classic_median_ms": med["classic"],
                       "fused_median_ms": med["fused"],
@@ -101,6 +109,8 @@ def main():
                       "config": {"entities": E, "relations": R, "dim": D, "batch": B, "neg": N,
                                  "neg_subject": NS, "gamma_entity": args.gamma_entity,
                                  "gamma_relation": args.gamma_relation,
+                                 "dropout_entity": args.dropout_entity,
+                                 "dropout_relation": args.dropout_relation,
                                  "steps": args.steps, "warmup": args.warmup}}), flush=True)
     worker.finalize()
     server.shutdown()

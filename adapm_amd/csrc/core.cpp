@@ -3766,6 +3766,135 @@ class Server {
     return loss;
   }
 
+  // word2vec window step (kernels.h, w2v_window_step_gpu). tok and starts
+  // are HOST int32 tensors: both are checked here, before anything is
+  // enqueued, and go up in one pinned blob with one asynchronous copy. keep
+  // and the alias table live on the store's device. On a CPU store the serial
+  // twins run on the caller's tensors.
+  struct WindowCall {
+    torch::Tensor blob, keep, prob, alias;  // keep the pointers of `a` alive
+    W2VWindowArgs a;
+  };
+  WindowCall window_call(const char* name, const torch::Tensor& tok, const torch::Tensor& starts,
+                         const c10::optional<torch::Tensor>& keep, const torch::Tensor& prob,
+                         const torch::Tensor& alias, int64_t W, int64_t N, uint64_t seed) {
+    TORCH_CHECK(num_keys_ % 2 == 0, name, ": the store holds syn0 and syn1 rows, 2 per word");
+    const int64_t V = num_keys_ / 2;
+    TORCH_CHECK(W >= 1 && W <= (1 << 20), name, ": window = ", W, " is outside 1..2^20");
+    TORCH_CHECK(N >= 0 && N <= W2V_WINDOW_MAX_NEG, name, ": N = ", N, " is outside 0..",
+                W2V_WINDOW_MAX_NEG);
+    auto host_i32 = [&](const torch::Tensor& t, const char* what) {
+      TORCH_CHECK(t.device().is_cpu() && t.scalar_type() == torch::kInt32 && t.dim() == 1 &&
+                      t.is_contiguous(),
+                  name, ": ", what, " must be a contiguous 1-d int32 CPU tensor");
+    };
+    host_i32(tok, "tok");
+    host_i32(starts, "starts");
+    const int64_t T = tok.numel(), S = starts.numel() - 1;
+    TORCH_CHECK(T < std::numeric_limits<int32_t>::max(), name, ": too many tokens");
+    TORCH_CHECK(S >= 0, name, ": starts must hold S + 1 >= 1 entries");
+    auto dev_t = [&](const torch::Tensor& t, torch::ScalarType st, int64_t len, const char* what) {
+      TORCH_CHECK(t.device() == dev_ && t.scalar_type() == st && t.dim() == 1 &&
+                      t.is_contiguous() && (len < 0 || t.numel() == len),
+                  name, ": ", what, " has the wrong device, dtype, layout or length");
+    };
+    dev_t(prob, torch::kFloat32, -1, "prob");
+    dev_t(alias, torch::kInt32, prob.numel(), "alias");
+    TORCH_CHECK(prob.numel() >= 1 && prob.numel() <= V, name, ": the alias table has ",
+                prob.numel(), " entries, the store ", V, " words");
+    if (keep) dev_t(*keep, torch::kFloat32, V, "keep");
+    const int32_t* sp = starts.data_ptr<int32_t>();
+    TORCH_CHECK(sp[0] == 0 && sp[S] == T, name, ": starts must run from 0 to len(tok)");
+    for (int64_t s = 0; s < S; ++s)
+      TORCH_CHECK(sp[s] <= sp[s + 1], name, ": starts decreases at sentence ", s);
+    const int32_t* tp = tok.data_ptr<int32_t>();
+    uint32_t bad = 0;
+    for (int64_t i = 0; i < T; ++i) bad |= (uint32_t)((uint64_t)(int64_t)tp[i] >= (uint64_t)V);
+    TORCH_CHECK(!bad, name, ": a token id lies outside [0, ", V, ")");
+
+    WindowCall wc;
+    wc.prob = prob, wc.alias = alias;
+    if (keep) wc.keep = *keep;
+    if (dev_.is_cuda()) {
+      auto pin = torch::empty({T + S + 1},
+                              torch::TensorOptions().dtype(torch::kInt32).pinned_memory(true));
+      std::memcpy(pin.data_ptr<int32_t>(), tp, T * sizeof(int32_t));
+      std::memcpy(pin.data_ptr<int32_t>() + T, sp, (S + 1) * sizeof(int32_t));
+      wc.blob = pin.to(dev_, /*non_blocking=*/true);
+      tp = wc.blob.data_ptr<int32_t>();
+      sp = tp + T;
+    }
+    wc.a = W2VWindowArgs{tp, sp, keep ? keep->data_ptr<float>() : nullptr,
+                         prob.data_ptr<float>(), alias.data_ptr<int32_t>(), T, S, prob.numel(),
+                         (int)W, (int)N, seed};
+    return wc;
+  }
+
+  std::tuple<torch::Tensor, torch::Tensor> w2v_window_step(
+      torch::Tensor tok, torch::Tensor starts, c10::optional<torch::Tensor> keep,
+      torch::Tensor prob, torch::Tensor alias, int64_t W, int64_t N, int64_t D, double lr,
+      double eps, uint64_t seed) {
+    const char* name = "w2v_window_step";
+    // check_fused_identity's guards, but for the device: a CPU store runs the twin
+    TORCH_CHECK(world_ == 1, name, " requires a single rank (all keys local)");
+    TORCH_CHECK(layout_identity_.load(), name, " requires the identity layout");
+    TORCH_CHECK(D >= 1 && D <= W2V_WINDOW_MAX_DIM, name, ": D = ", D, " is outside 1..",
+                W2V_WINDOW_MAX_DIM, "; longer rows take the pair path");
+    TORCH_CHECK(uniform_len_ == 2 * D, name, ": store rows must be [emb|accum] = 2D");
+    auto wc = window_call(name, tok, starts, keep, prob, alias, W, N, seed);
+    const int64_t T = wc.a.T;
+    auto loss = torch::empty({T}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    auto counts = torch::empty({2}, torch::TensorOptions().dtype(torch::kInt32).device(dev_));
+    {
+      InflightGuard g(this);
+      if (dev_.is_cuda()) {
+        auto work = torch::empty({w2v_window_work_words(T)},
+                                 torch::TensorOptions().dtype(torch::kInt32).device(dev_));
+        w2v_window_step_gpu(slab_.data, Slab::padded(uniform_len_), wc.a, (int)D, (float)lr,
+                            (float)eps, work.data_ptr<int32_t>(), loss.data_ptr<float>(),
+                            counts.data_ptr<int32_t>(), current_stream(dev_));
+      } else {
+        std::lock_guard<std::mutex> vg(cpu_val_mu_);
+        w2v_window_step_cpu(slab_.data, Slab::padded(uniform_len_), wc.a, (int)D, (float)lr,
+                            (float)eps, loss.data_ptr<float>(), counts.data_ptr<int32_t>());
+      }
+    }
+    // the key count stays on the device; the stats take the upper bound
+    count_fused_ops(T * (1 + 2 * W * (1 + N)));
+    return {loss, counts};
+  }
+
+  // The same plan, materialised: (ctr[P], ctx[P], neg[P][N], counts) as
+  // int64 word ids on the store's device. This entry reads counts back to
+  // cut the buffers to P pairs; it is the path for stores the window step
+  // does not serve, and never touches the slab.
+  std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor> w2v_window_pairs(
+      torch::Tensor tok, torch::Tensor starts, c10::optional<torch::Tensor> keep,
+      torch::Tensor prob, torch::Tensor alias, int64_t W, int64_t N, uint64_t seed) {
+    const char* name = "w2v_window_pairs";
+    auto wc = window_call(name, tok, starts, keep, prob, alias, W, N, seed);
+    const int64_t T = wc.a.T, cap = T * 2 * W;
+    TORCH_CHECK(cap < std::numeric_limits<int32_t>::max(), name, ": T * 2W = ", cap,
+                " pairs do not fit one call");
+    auto i64 = torch::TensorOptions().dtype(torch::kInt64).device(dev_);
+    auto ctr = torch::empty({cap}, i64), ctx = torch::empty({cap}, i64);
+    auto neg = torch::empty({cap * N}, i64);
+    auto counts = torch::empty({2}, torch::TensorOptions().dtype(torch::kInt32).device(dev_));
+    if (dev_.is_cuda()) {
+      auto work = torch::empty({w2v_window_work_words(T)},
+                               torch::TensorOptions().dtype(torch::kInt32).device(dev_));
+      w2v_window_pairs_gpu(wc.a, work.data_ptr<int32_t>(), ctr.data_ptr<int64_t>(),
+                           ctx.data_ptr<int64_t>(), neg.data_ptr<int64_t>(),
+                           counts.data_ptr<int32_t>(), current_stream(dev_));
+    } else {
+      w2v_window_pairs_cpu(wc.a, ctr.data_ptr<int64_t>(), ctx.data_ptr<int64_t>(),
+                           neg.data_ptr<int64_t>(), counts.data_ptr<int32_t>());
+    }
+    const int64_t P = counts.cpu().data_ptr<int32_t>()[1];
+    return {ctr.narrow(0, 0, P), ctx.narrow(0, 0, P), neg.narrow(0, 0, P * N).view({P, N}),
+            counts};
+  }
+
   torch::Tensor mf_step_fused(torch::Tensor keys_w, torch::Tensor keys_h, torch::Tensor x,
                               int64_t R, double lr, double lambda, double eps) {
     check_fused_identity("mf_step_fused", R);
@@ -5137,6 +5266,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("CTR_MAX_DIM") = (int)CTR_MAX_DIM;
   m.attr("RESCAL_FUSED_MAX_DIM") = (int)RESCAL_FUSED_MAX_DIM;
   m.attr("RESCAL_DROP_MAX_DIM") = (int)RESCAL_DROP_MAX_DIM;
+  m.attr("W2V_WINDOW_MAX_DIM") = (int)W2V_WINDOW_MAX_DIM;
+  m.attr("W2V_SCAN_BLOCK") = (int)W2V_SCAN_BLOCK;
   py::class_<CtrBatch, std::shared_ptr<CtrBatch>>(m, "CtrBatch")
       .def("__len__", [](const CtrBatch& b) { return b.n; });
   py::class_<Server>(m, "Server")
@@ -5177,6 +5308,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
            py::call_guard<py::gil_scoped_release>())
       .def("w2v_step_fused", &Server::w2v_step_fused, py::call_guard<py::gil_scoped_release>())
       .def("mf_step_fused", &Server::mf_step_fused, py::call_guard<py::gil_scoped_release>())
+      .def("w2v_window_step", &Server::w2v_window_step, py::arg("tok"), py::arg("starts"),
+           py::arg("keep"), py::arg("prob"), py::arg("alias"), py::arg("W"), py::arg("N"),
+           py::arg("D"), py::arg("lr"), py::arg("eps"), py::arg("seed"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("w2v_window_pairs", &Server::w2v_window_pairs, py::arg("tok"), py::arg("starts"),
+           py::arg("keep"), py::arg("prob"), py::arg("alias"), py::arg("W"), py::arg("N"),
+           py::arg("seed"), py::call_guard<py::gil_scoped_release>())
       .def("ctr_lookup_fused", &Server::ctr_lookup_fused, py::arg("keys"), py::arg("dim"),
            py::call_guard<py::gil_scoped_release>())
       .def("ctr_update_fused", &Server::ctr_update_fused, py::arg("batch"), py::arg("grad"),

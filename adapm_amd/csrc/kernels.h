@@ -550,6 +550,109 @@ void w2v_sgns_step_cpu(const float* ctr, const float* ctx, const float* neg, flo
                        float* dctx, float* dneg, float* loss, int B, int N, int D, float lr,
                        float eps);
 
+// word2vec WINDOW step (w2v_window_hip.hip; reference word2vec.cc:679-745, one
+// context window per sentence position): a token stream goes in, and the
+// subsampling, the windows, the pairs and the negatives are made where they
+// are used.
+//
+// Inputs of one call (W2VWindowArgs)
+//   tok[T]       int32 word ids in [0, V), in corpus order
+//   starts[S+1]  int32, non-decreasing, starts[0] = 0, starts[S] = T; sentence
+//                s is [starts[s], starts[s+1]), empty sentences allowed
+//   keep[V]      float keep probabilities, or null for none
+//   prob[n], alias[n]  the unigram alias table of sampling.py, n <= V
+//   W >= 1, 0 <= N <= 63, a 64-bit seed
+// GOLD = 0x9e3779b97f4a7c15 and sd[k] = pcg_hash64(seed + k), k = 0, 1, 2, in
+// wrapping 64-bit arithmetic; pcg_hash64 is alias_draw's.
+//
+// Rules
+//  1 Subsample. Position p is kept iff u < keep[tok[p]], with
+//    h = pcg_hash64(sd[0] ^ p*GOLD) and u = float((h >> 40) & 0xffffff) * 2^-24
+//    (the bits alias_draw uses for its u). A null keep keeps everything.
+//  2 Compact. Kept tokens keep their order; c is a token's index among the
+//    kept ones, ctok[c] its word, a sentence is its kept tokens, n_kept their
+//    number.
+//  3 Window. For centre c, b = 1 + pcg_hash64(sd[1] ^ c*GOLD) % W.
+//  4 Pairs. For a = W-b .. W+b, a != W, ascending, j = c - W + a; if j lies in
+//    c's compacted sentence, (ctr = ctok[c], ctx = ctok[j]) is a pair.
+//  5 Negatives. Draw d < N of that pair is alias_draw's rule (slot = h % n,
+//    u from bits 40..63, word = u < prob[slot] ? slot : alias[slot]) on
+//    h = pcg_hash64(sd[2] ^ ((c*(2W+1) + a)*N + d) * GOLD). A draw equal to the
+//    centre is not skipped (the pair steps do not skip it either).
+//  6 Rows. The centre row has key 2*ctr (syn0), a target row key 2*w + 1
+//    (syn1). Identity layout, one rank: key k is row k of the slab, rows are
+//    [emb(D) | acc(D)] and `plen` floats apart.
+//  7 Step of a centre. Its row is read once. For each of its pairs in order,
+//    and for target t = 0 (ctx, y = +1), then t = 1..N (y = -1):
+//      dot = c_emb . x_emb,  g = -y * sigmoid(-y * dot)
+//      the target gets one AdaGrad update of g * c_emb, written as atomics
+//      (delta and g^2, the accumulator read with a plain load before them)
+//      a_c += g * x_emb
+//  8 Centre update. After a pair's 1 + N targets the centre gets one AdaGrad
+//    update of a_c, applied to the held copy (emb and acc both); the next
+//    pair scores against it, as the reference's per-pair syn0 update does.
+//    After the last pair `held - read` of both halves is added to the slab
+//    with atomics. A centre without pairs writes nothing.
+//  9 Outputs. loss[c] sums the softplus terms of all of c's pairs (log(1 +
+//    exp(-y dot)), the sides kernels' softplus1pf on the GPU), loss[c] = 0 for
+//    n_kept <= c < T; counts[0] = n_kept, counts[1] = number of pairs, both
+//    on the device. Nothing comes back to the host; no entry synchronises.
+//
+// Hogwild contract, as for every fused step: rows named by several centres
+// see concurrent updates (in a window that is every syn1 row of a sentence
+// longer than two). Within a centre the GPU kernel has the next target's row
+// in flight while the current one is written, so a draw that repeats the
+// target just before it in the same pair reads that row as it was. The CPU
+// twins are serial, in compacted order and in place.
+//
+// GPU launches, all on `stream`. An exclusive int32 scan of n items is a
+// block scan (W2V_SCAN_BLOCK items per workgroup, in LDS) that leaves block
+// totals, and one workgroup that scans the totals; readers add the two.
+//   plan   scan of the keep flags over T + 1 items (item T is 0, so the scan
+//          value there is n_kept); then one thread per position writes
+//          ctok[c] and the compacted bounds [lo[c], hi[c]) of its sentence,
+//          found by binary search of p in starts, zeroes loss[c >= n_kept]
+//          and sets counts. Grids are sized by T; surplus waves exit.
+//   step   k_w2v_window_step: one wave per centre, four per workgroup, no LDS
+//          and no barrier. With D % 4 == 0 lane l holds float4 columns
+//          4*(l + 64*v), v < ceil(D/256), else scalar columns l + 64*i for
+//          i < 1, 2, 4 or 8 covering D. The 1 + N target words of a pair are
+//          made lane-parallel (lane 0 ctx, lane d+1 draw d) and broadcast
+//          target by target; the dot is a six-step xor-shuffle reduction.
+//   pairs  w2v_window_pairs: the same plan, then a scan of the per-centre pair
+//          counts and one thread per centre writing ctr[P], ctx[P], neg[P*N]
+//          as int64 WORD ids ordered by (c, a). The buffers hold T*2W pairs.
+//          This feeds the pair steps where the window step does not apply.
+// `work` is w2v_window_work_words(T) int32 words on the device, contents
+// irrelevant. 1 <= D <= W2V_WINDOW_MAX_DIM, T < 2^31 (for pairs T*2W < 2^31);
+// callers check, and check tok and starts on the host. T == 0 is a no-op that
+// still sets counts.
+constexpr int W2V_WINDOW_MAX_DIM = 512;
+constexpr int W2V_WINDOW_MAX_NEG = 63;
+constexpr int W2V_SCAN_BLOCK = 1024;
+struct W2VWindowArgs {
+  const int32_t* tok;
+  const int32_t* starts;
+  const float* keep;  // may be null
+  const float* prob;
+  const int32_t* alias;
+  int64_t T, S, n;
+  int W, N;
+  uint64_t seed;
+};
+inline int64_t w2v_window_work_words(int64_t T) {
+  const int64_t nb = (T + W2V_SCAN_BLOCK) / W2V_SCAN_BLOCK;  // blocks over T + 1 items
+  return 2 * (T + 1 + nb) + 3 * T;
+}
+void w2v_window_step_gpu(float* slab, int32_t plen, const W2VWindowArgs& a, int D, float lr,
+                         float eps, int32_t* work, float* loss, int32_t* counts, void* stream);
+void w2v_window_pairs_gpu(const W2VWindowArgs& a, int32_t* work, int64_t* ctr, int64_t* ctx,
+                          int64_t* neg, int32_t* counts, void* stream);
+void w2v_window_step_cpu(float* slab, int32_t plen, const W2VWindowArgs& a, int D, float lr,
+                         float eps, float* loss, int32_t* counts);
+void w2v_window_pairs_cpu(const W2VWindowArgs& a, int64_t* ctr, int64_t* ctx, int64_t* neg,
+                          int32_t* counts);
+
 // Matrix-factorization NZSL step: per nonzero (i, j, x):
 //  w: [B][2R] row-factor rows, h: [B][2R] col-factor rows (R = rank)
 //  outputs dw, dh (push deltas), loss [B] squared error

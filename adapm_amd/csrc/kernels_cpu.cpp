@@ -1030,4 +1030,123 @@ void rescal_step_sides_cpu(const float* s, const float* r, const float* o, const
   }
 }
 
+// ---- word2vec window step (kernels.h, w2v_window_step): rules 1-5 as one
+// serial walk that hands every pair to `on_pair(c, a, ctr, ctx)` and every
+// centre's end to `on_centre(c, ctr, pairs)`, in compacted order.
+
+namespace {
+
+struct WindowWalk {
+  const W2VWindowArgs& a;
+  uint64_t sd[3];
+  std::vector<int32_t> ctok, lo, hi;
+
+  explicit WindowWalk(const W2VWindowArgs& a_) : a(a_) {
+    for (int k = 0; k < 3; ++k) sd[k] = pcg_hash64_c(a.seed + k);
+    for (int64_t s = 0; s < a.S; ++s) {
+      const int32_t first = (int32_t)ctok.size();
+      for (int64_t p = a.starts[s]; p < a.starts[s + 1]; ++p) {
+        if (a.keep) {
+          uint64_t h = pcg_hash64_c(sd[0] ^ (uint64_t)p * 0x9e3779b97f4a7c15ULL);
+          float u = (float)((h >> 40) & 0xffffff) * (1.0f / 16777216.0f);
+          if (!(u < a.keep[a.tok[p]])) continue;
+        }
+        ctok.push_back(a.tok[p]);
+      }
+      lo.resize(ctok.size(), first);
+      hi.resize(ctok.size(), (int32_t)ctok.size());
+    }
+  }
+
+  int64_t draw(int64_t c, int w, int d) const {
+    const uint64_t idx =
+        ((uint64_t)c * (uint64_t)(2 * a.W + 1) + (uint64_t)w) * (uint64_t)a.N + (uint64_t)d;
+    uint64_t h = pcg_hash64_c(sd[2] ^ idx * 0x9e3779b97f4a7c15ULL);
+    uint64_t slot = h % (uint64_t)a.n;
+    float u = (float)((h >> 40) & 0xffffff) * (1.0f / 16777216.0f);
+    return u < a.prob[slot] ? (int64_t)slot : (int64_t)a.alias[slot];
+  }
+
+  template <typename P, typename C>
+  int64_t run(P&& on_pair, C&& on_centre) const {
+    int64_t pairs = 0;
+    for (int64_t c = 0; c < (int64_t)ctok.size(); ++c) {
+      const int b =
+          1 + (int)(pcg_hash64_c(sd[1] ^ (uint64_t)c * 0x9e3779b97f4a7c15ULL) % (uint64_t)a.W);
+      int np = 0;
+      for (int w = a.W - b; w <= a.W + b; ++w) {
+        const int64_t j = c - a.W + w;
+        if (w == a.W || j < lo[c] || j >= hi[c]) continue;
+        on_pair(c, w, ctok[c], ctok[j]);
+        ++np;
+      }
+      on_centre(c, ctok[c], np);
+      pairs += np;
+    }
+    return pairs;
+  }
+};
+
+}  // namespace
+
+void w2v_window_pairs_cpu(const W2VWindowArgs& a, int64_t* ctr, int64_t* ctx, int64_t* neg,
+                          int32_t* counts) {
+  WindowWalk ww(a);
+  int64_t q = 0;
+  counts[1] = (int32_t)ww.run(
+      [&](int64_t c, int w, int32_t wc, int32_t wx) {
+        ctr[q] = wc;
+        ctx[q] = wx;
+        for (int d = 0; d < a.N; ++d) neg[q * a.N + d] = ww.draw(c, w, d);
+        ++q;
+      },
+      [](int64_t, int32_t, int) {});
+  counts[0] = (int32_t)ww.ctok.size();
+}
+
+void w2v_window_step_cpu(float* slab, int32_t plen, const W2VWindowArgs& a, int D, float lr,
+                         float eps, float* loss, int32_t* counts) {
+  WindowWalk ww(a);
+  std::vector<float> ce(D), ca(D), ac(D);
+  std::fill(loss, loss + a.T, 0.f);
+  int64_t held = -1;  // the centre whose row is in ce / ca
+  float lsum = 0.f;
+  counts[1] = (int32_t)ww.run(
+      [&](int64_t c, int w, int32_t wc, int32_t wx) {
+        float* cb = slab + 2 * (int64_t)wc * plen;
+        if (held != c) {  // rule 7: read once
+          std::copy(cb, cb + D, ce.begin());
+          std::copy(cb + D, cb + 2 * D, ca.begin());
+          held = c;
+          lsum = 0.f;
+        }
+        std::fill(ac.begin(), ac.end(), 0.f);
+        for (int t = 0; t <= a.N; ++t) {
+          const int64_t word = t == 0 ? (int64_t)wx : ww.draw(c, w, t - 1);
+          float* xb = slab + (2 * word + 1) * plen;
+          float dot = 0.f;
+          for (int k = 0; k < D; ++k) dot += ce[k] * xb[k];
+          const float z = t == 0 ? -dot : dot;
+          const float g = t == 0 ? -sigmoidf_(z) : sigmoidf_(z);
+          lsum += softplusf_(z);
+          for (int k = 0; k < D; ++k) {
+            ac[k] += g * xb[k];
+            adagrad_inplace(xb[k], xb[D + k], g * ce[k], lr, eps);
+          }
+        }
+        for (int k = 0; k < D; ++k) adagrad_inplace(ce[k], ca[k], ac[k], lr, eps);  // rule 8
+      },
+      [&](int64_t c, int32_t wc, int np) {
+        if (!np) return;
+        float* cb = slab + 2 * (int64_t)wc * plen;
+        // held - read is what the centre's own pairs did to it; targets are
+        // syn1 rows, so in a serial walk nothing else has touched this syn0
+        // row and the held copy is the result
+        std::copy(ce.begin(), ce.end(), cb);
+        std::copy(ca.begin(), ca.end(), cb + D);
+        loss[c] = lsum;
+      });
+  counts[0] = (int32_t)ww.ctok.size();
+}
+
 }  // namespace adapm

@@ -8,6 +8,9 @@ Rebuild of the reference app (reference apps/word2vec.cc):
   - sentence look-ahead intent prefetch (reference :563-618)
   - fused SGNS step kernel (kernels_hip.hip k_w2v_step; reference
     :679-745)
+  - window step from a token stream (w2v_window_hip.hip; the reference's
+    loop shape, one context window per sentence position): subsampling,
+    windows, pairs and negatives made on the device (train_tokens_fused)
   - checkpoint: word2vec text-format embedding export (reference
     :367-416)
 """
@@ -59,6 +62,8 @@ class Word2Vec(StepModel):
     def __init__(self, cfg: W2VConfig, server, worker):
         super().__init__(cfg, server, worker)
         self._keep_prob = None
+        self._keep_dev = None  # _keep_prob as fp32 on the store's device
+        self.last_counts = None
         self.words = None  # real-corpus vocab strings (data_io.build_vocab)
 
     def init_embeddings(self):
@@ -81,6 +86,7 @@ class Word2Vec(StepModel):
         with np.errstate(divide="ignore"):
             keep = np.sqrt(sample / f) + sample / f
         self._keep_prob = np.minimum(1.0, keep)
+        self._keep_dev = None
 
     def pairs_from_sentences(self, sentences):
         """(center, context) pairs with the reference's shrinking window,
@@ -148,6 +154,62 @@ class Word2Vec(StepModel):
                   neg_words.reshape(B, cfg.negative))
         return self._fused_step(arrays, sync_loss, force_general)
 
+    # ------------------------------------------------ token-stream training
+
+    _window_calls = 0  # window launches so far: the step counter of the seed
+
+    def _window_args(self, tokens, starts):
+        """(tok, starts, keep, prob, alias, window, negative, seed) of the next
+        window call. Every call takes seed = mix64(mix64(mix64(cfg.seed) ^ rank)
+        ^ n), n = 1, 2, ... counting this model's window calls (the rule of
+        kge._drop_tail): two models with equal seeds make equal pairs."""
+        from .kge import _mix64
+
+        cfg = self.cfg
+        dist = self.server.sampling.dist if self.server.sampling is not None else None
+        if dist is None or not hasattr(dist, "alias") or dist.key_of is not None:
+            raise RuntimeError("train_tokens_fused draws its negatives from the server's "
+                               "unigram sampler over word ids 0..V")
+        if self._keep_prob is not None and self._keep_dev is None:
+            self._keep_dev = torch.from_numpy(self._keep_prob.astype(np.float32)).to(self.dev)
+        self._window_calls += 1
+        seed = _mix64(_mix64(_mix64(cfg.seed) ^ self.rank) ^ self._window_calls)
+        tok = torch.from_numpy(np.ascontiguousarray(tokens, dtype=np.int32))
+        st = torch.from_numpy(np.ascontiguousarray(starts, dtype=np.int32))
+        return (tok, st, self._keep_dev, dist.prob.to(self.dev), dist.alias.to(self.dev),
+                cfg.window, cfg.negative, seed)
+
+    def train_tokens_fused(self, tokens, starts, sync_loss=False):
+        """One step over a token stream: `tokens` are word ids in corpus
+        order, sentence s is tokens[starts[s]:starts[s+1]]. Subsampling,
+        windows, pairs and negatives are made on the device (kernels.h,
+        w2v_window_step). With one rank and the identity layout the window
+        kernel trains on the slab itself; otherwise Server.w2v_window_pairs
+        makes the same pairs and batch_pairs-sized slices of them, with
+        their drawn negatives, go through the fused pair step.
+
+        Returns the per-centre (window kernel) or per-pair losses without a
+        host sync, or with sync_loss the mean loss per pair. `last_counts`
+        holds (kept tokens, pairs) of the call as a device tensor."""
+        cfg = self.cfg
+        raw = self.server.raw
+        tok, st, keep, prob, alias, W, N, seed = self._window_args(tokens, starts)
+        if self.world == 1 and raw.layout_identity() and cfg.dim <= _C.W2V_WINDOW_MAX_DIM:
+            loss, self.last_counts = raw.w2v_window_step(tok, st, keep, prob, alias, W, N,
+                                                         cfg.dim, cfg.lr, cfg.eps, seed)
+        else:
+            ctr, ctx, neg, self.last_counts = raw.w2v_window_pairs(tok, st, keep, prob, alias,
+                                                                   W, N, seed)
+            ctr, ctx, neg = (t.cpu().numpy() for t in (ctr, ctx, neg))
+            parts = [self._fused_step((ctr[i:i + cfg.batch_pairs], ctx[i:i + cfg.batch_pairs],
+                                       neg[i:i + cfg.batch_pairs]), False, False)
+                     for i in range(0, len(ctr), cfg.batch_pairs)]
+            loss = torch.cat(parts) if parts else torch.zeros(0, device=self.dev)
+        if not sync_loss:
+            return loss
+        pairs = int(self.last_counts[1].item())
+        return float(loss.sum().item()) / pairs if pairs else 0.0
+
     def export_text(self, path: str, max_words: int = None, chunk: int = 65536):
         """word2vec text format: '<vocab> <dim>' header then word vectors
         (reference word2vec.cc:367-416)."""
@@ -198,6 +260,21 @@ def make_synthetic_sentences(n_sentences, vocab_size, mean_len=12, zipf_a=1.2, s
     return out
 
 
+def token_chunks(sentences, chunk_tokens):
+    """[(tokens, starts)]: the sentences as int32 token streams of about
+    chunk_tokens tokens each, whole sentences only, for train_tokens_fused."""
+    out, cur, n = [], [], 0
+    for s in list(sentences) + [None]:
+        if cur and (s is None or n + len(s) > chunk_tokens):
+            starts = np.concatenate([[0], np.cumsum([len(x) for x in cur])]).astype(np.int32)
+            out.append((np.concatenate(cur).astype(np.int32), starts))
+            cur, n = [], 0
+        if s is not None:
+            cur.append(s)
+            n += len(s)
+    return out
+
+
 def main():
     """CLI (rebuild of reference apps/word2vec.cc): SGNS on a synthetic
     corpus with subsampling + unigram negatives; exports embeddings."""
@@ -222,6 +299,11 @@ def main():
                          "file, reference LearnVocabFromTrainFile); default: synthetic")
     ap.add_argument("--min-count", type=int, default=5)
     ap.add_argument("--device", type=str, default=None)
+    ap.add_argument("--device-pairs", action="store_true",
+                    help="train from the token stream: subsampling, windows, pairs and "
+                         "negatives are made on the device (train_tokens_fused)")
+    ap.add_argument("--chunk-tokens", type=int, default=65536,
+                    help="with --device-pairs: tokens per call, in whole sentences")
     a = ap.parse_args()
 
     words = None
@@ -252,7 +334,26 @@ def main():
                  if i % world == rank]  # sentence partition (reference file-offset split)
     else:
         sents = make_synthetic_sentences(a.sentences // world, a.vocab, seed=rank)
-    for ep in range(a.epochs):
+    chunks = token_chunks(sents, a.chunk_tokens) if a.device_pairs else []
+    for ep in range(a.epochs if a.device_pairs else 0):
+        t0 = time.time()
+        loss_sum = torch.zeros((), dtype=torch.float64, device=model.dev)
+        done = torch.zeros(2, dtype=torch.int64, device=model.dev)
+        for tokens, starts in chunks:
+            if world > 1:
+                model.signal_intent([tokens], worker.current_clock() + 1,
+                                    worker.current_clock() + 3)
+            loss_sum += model.train_tokens_fused(tokens, starts).sum()
+            done += model.last_counts
+            worker.advance_clock()
+        model.drain()
+        kept, pairs = (int(x) for x in done.tolist())  # the epoch's one host sync
+        total = worker.allreduce(float(loss_sum.item()) / max(pairs, 1))
+        if rank == 0:
+            dt = time.time() - t0
+            print(f"[w2v] epoch {ep}: loss {total / world:.4f} ({kept} words, {pairs} pairs, "
+                  f"{dt:.1f}s, {sum(len(t) for t, _ in chunks) / dt:.0f} words/s)")
+    for ep in range(0 if a.device_pairs else a.epochs):
         t0 = time.time()
         ctr, ctx = model.pairs_from_sentences(sents)
         losses = []

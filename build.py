@@ -37,19 +37,21 @@ SOURCES = [
     "rescal_fused_hip.hip",
     "kge_drop_hip.hip",
     "rescal_drop_hip.hip",
+    "w2v_window_hip.hip",
     "kernels_cpu.cpp",
 ]
 
 # Per-source flags. ctr_hip.hip adds float4 lanes element by element; it,
-# rescal_fused_hip.hip, kge_drop_hip.hip and rescal_drop_hip.hip (float4
-# column sums, element by element) are built without the packed fp32
-# instructions.
+# rescal_fused_hip.hip, kge_drop_hip.hip, rescal_drop_hip.hip (float4 column
+# sums, element by element) and w2v_window_hip.hip (float4 lanes of a row)
+# are built without the packed fp32 instructions.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "ctr_hip.hip": NO_PACKED_FP32,
     "rescal_fused_hip.hip": NO_PACKED_FP32,
     "kge_drop_hip.hip": NO_PACKED_FP32,
     "rescal_drop_hip.hip": NO_PACKED_FP32,
+    "w2v_window_hip.hip": NO_PACKED_FP32,
 }
 
 MODULE = "_C"

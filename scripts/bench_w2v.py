@@ -14,6 +14,58 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def bench_tokens(args, model, server, worker):
+    """Corpus throughput: words/s and pairs/s from sentences to trained pairs,
+    pair generation included."""
+    from adapm_amd.models.word2vec import make_synthetic_sentences, token_chunks
+
+    total = args.warmup + args.steps
+    sents = make_synthetic_sentences(int(total * args.tokens / 11) + 64, args.vocab, seed=2000)
+    chunks = token_chunks(sents, args.tokens)[:total]
+    assert len(chunks) == total, "too few synthetic sentences for the requested steps"
+    is_cuda = server.rt.device.type == "cuda"
+    bp = model.cfg.batch_pairs
+    pairs = torch.zeros((), dtype=torch.int64, device=server.rt.device)
+
+    def step(tok, starts):
+        nonlocal pairs
+        if not args.host_pairs:
+            model.train_tokens_fused(tok, starts)
+            pairs += model.last_counts[1]
+            return
+        ctr, ctx = model.pairs_from_sentences(
+            [tok[a:b].astype(np.int64) for a, b in zip(starts[:-1], starts[1:])])
+        for i in range(0, len(ctr), bp):
+            model.train_pairs_fused(ctr[i:i + bp], ctx[i:i + bp])
+        pairs += len(ctr)
+
+    for c in chunks[:args.warmup]:
+        step(*c)
+    model.drain()
+    if is_cuda:
+        torch.cuda.synchronize()
+    pairs.zero_()
+    t0 = time.perf_counter()
+    for c in chunks[args.warmup:]:
+        step(*c)
+    model.drain()
+    if is_cuda:
+        torch.cuda.synchronize()
+    el = time.perf_counter() - t0
+    words = sum(len(t) for t, _ in chunks[args.warmup:])
+    print(json.dumps({
+        "metric": "sgns_corpus_words_per_s", "value": words / el, "unit": "words/s",
+        "pairs_per_s": int(pairs.item()) / el, "pairs": int(pairs.item()), "words": words,
+        "ms_per_chunk": 1000 * el / args.steps, "steps": args.steps, "warmup": args.warmup,
+        "higher_is_better": True, "dtype": "fp32", "data": "synthetic",
+        "config": {"model": "word2vec_sgns", "pairs_made": "host" if args.host_pairs else "device",
+                   "vocab": args.vocab, "dim": args.dim, "window": args.window,
+                   "negative": args.negative, "chunk_tokens": args.tokens},
+    }), flush=True)
+    worker.finalize()
+    server.shutdown()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -26,6 +78,13 @@ def main():
     ap.add_argument("--device", type=str, default=None)
     ap.add_argument("--no-fused", action="store_true",
                     help="disable the fused slab-direct kernel (single-rank GPU fast path)")
+    ap.add_argument("--tokens", type=int, default=0,
+                    help="time corpus training instead: synthetic sentences in chunks of this "
+                         "many tokens through train_tokens_fused (pairs made on the device)")
+    ap.add_argument("--host-pairs", action="store_true",
+                    help="with --tokens: the same chunks through pairs_from_sentences and "
+                         "train_pairs_fused (pairs made in Python)")
+    ap.add_argument("--window", type=int, default=5)
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -34,7 +93,8 @@ def main():
     import adapm_amd
     from adapm_amd.models.word2vec import W2VConfig, Word2Vec
 
-    cfg = W2VConfig(vocab_size=args.vocab, dim=args.dim, negative=args.negative)
+    cfg = W2VConfig(vocab_size=args.vocab, dim=args.dim, negative=args.negative,
+                    window=args.window)
     adapm_amd.setup(num_keys=cfg.num_keys, num_threads=1, device=args.device,
                     capacity_factor=2.0, max_sync_per_sec=2000.0)
     server = adapm_amd.Server(cfg.row)
@@ -44,6 +104,9 @@ def main():
     model = Word2Vec(cfg, server, worker)
     model.set_vocab_counts(counts)
     model.init_embeddings()
+
+    if args.tokens:
+        return bench_tokens(args, model, server, worker)
 
     rng = np.random.default_rng(2000 + rank)
     # training pairs follow the SUBSAMPLED word distribution (reference

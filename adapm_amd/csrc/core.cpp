@@ -3705,6 +3705,8 @@ class Server {
                                                                  double eps) {
     TORCH_CHECK(uniform_len_ == 2 * R, "mf_step_fused: store rows must be [emb|accum] = 2R");
     TORCH_CHECK(x.scalar_type() == torch::kFloat32, "ratings must be float32");
+    // compacted to the hit samples on the host, below
+    TORCH_CHECK(x.device().is_cpu(), "mf_step_fused: ratings must be a CPU tensor");
     const int64_t B = keys_w.numel();
     TORCH_CHECK(x.numel() == B);
     return step_fused_general(

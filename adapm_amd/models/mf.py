@@ -98,8 +98,9 @@ class MF(StepModel):
         zero-host-work kernel (Server.mf_step_fused); otherwise the
         general offsets path runs the fused kernel on all-local nonzeros
         and routes the remote remainder through the classic path."""
-        arrays = (np.asarray(rows, dtype=np.int64), np.asarray(cols, dtype=np.int64),
-                  np.asarray(ratings, dtype=np.float32))
+        arrays = (np.ascontiguousarray(rows, dtype=np.int64),
+                  np.ascontiguousarray(cols, dtype=np.int64),
+                  np.ascontiguousarray(ratings, dtype=np.float32))
         return self._fused_step(arrays, sync_loss, force_general)
 
     # -------------------------------------------------- schedules

@@ -88,6 +88,20 @@ static void check_step_lanes(const char* name, const char* what, int64_t lanes) 
               " exceeds the GPU step kernels' limit of ", STEP_MAX_LANES);
 }
 
+// What every chunk entry checks of C, M and D (kernels.h,
+// kge_complex_step_chunk); the GPU entries also need D % 8 == 0.
+static void check_chunk_shape(const char* name, int64_t C, int64_t M, int64_t D, bool gpu) {
+  TORCH_CHECK(C >= 1 && C <= KGE_CHUNK_MAX_C, name, ": C = ", C, " must be in [1, ",
+              (int)KGE_CHUNK_MAX_C, "]");
+  TORCH_CHECK(M >= 1 && M <= KGE_CHUNK_MAX_M, name, ": M = ", M, " must be in [1, ",
+              (int)KGE_CHUNK_MAX_M, "]");
+  TORCH_CHECK(D >= 2 && D % 2 == 0 && D <= (1 << 24), name, ": D = ", D,
+              " must be even, >= 2 and <= 2^24");
+  if (gpu)
+    TORCH_CHECK(D % 8 == 0, name, ": D = ", D,
+                " must be a multiple of 8 on the GPU (16-byte aligned halves of a row)");
+}
+
 // Dropout probabilities of the ComplEx drop step -> 10-bit thresholds
 // (kernels.h): refused unless lround(p * 1024) lies in [0, 1023].
 static std::pair<int, int> check_drop(const char* name, double p_e, double p_r) {
@@ -3135,6 +3149,93 @@ class Server {
                                      lr, eps, gamma_e, gamma_r);
   }
 
+  // The step with chunk-shared negatives (kernels.h, kge_complex_step_chunk)
+  // on the identity path, beside kge_step_sides_fused_impl and pass for pass
+  // like it: arguments first, so that a bad call is refused on any store, all
+  // host keys one staged blob whose upload is the tag pass, then the flag and
+  // bits passes over the 3B + n_chunks * M occurrences and the two launches.
+  // What differs is the number of negatives, n_chunks * M, and the scratch.
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_chunk_fused_impl(
+      const torch::Tensor& keys_s, const torch::Tensor& keys_r, const torch::Tensor& keys_o,
+      const torch::Tensor* keys_neg, UniformStream* us, int64_t C, int64_t M, int64_t D,
+      double lr, double eps) {
+    const char* name = us ? "kge_step_chunk_fused_sampled" : "kge_step_chunk_fused";
+    check_chunk_shape(name, C, M, D, true);
+    const int64_t B = keys_s.numel();
+    TORCH_CHECK(keys_r.numel() == B && keys_o.numel() == B, name,
+                ": key arrays disagree on the batch");
+    const int64_t n_neg = (B + C - 1) / C * M;
+    // the tag pass numbers the occurrences in 32 bits, ROWTAG_SHARED aside
+    TORCH_CHECK(B < ((int64_t)1 << 31) && 3 * B + n_neg < (int64_t)ROWTAG_SHARED, name,
+                ": too many keys in one step");
+    if (!us)
+      TORCH_CHECK(keys_neg->numel() == n_neg, name, ": keys_neg must hold ceil(B/C) * M = ",
+                  n_neg, " keys");
+    check_fused_identity(name, D);
+    auto loss = torch::empty({B}, torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    if (B == 0)
+      return {loss, torch::empty({0}, torch::TensorOptions().dtype(torch::kInt64).device(dev_))};
+    HostKeys hk;
+    StagedKeys sk;
+    torch::Tensor drawn;
+    const int64_t* kn = nullptr;
+    if (us) {
+      TORCH_CHECK(us->lo() >= 0 && us->hi() <= num_keys_, name, ": stream range [", us->lo(),
+                  ", ", us->hi(), ") exceeds the store's ", num_keys_, " keys");
+      TORCH_CHECK(us->device() == dev_, name, ": stream is not on the store's device");
+      hk = host_keys({&keys_s, &keys_r, &keys_o});
+      drawn = us->draw(n_neg);
+      kn = drawn.data_ptr<int64_t>();
+    } else {
+      hk = host_keys({&keys_s, &keys_r, &keys_o, keys_neg});
+    }
+    const int64_t n_dev = us ? n_neg : 0;
+
+    auto scratch = torch::empty({kge_chunk_scratch_floats(B, M)},
+                                torch::TensorOptions().dtype(torch::kFloat32).device(dev_));
+    void* st = current_stream(dev_);
+    {
+      InflightGuard g(this);
+      std::unique_lock<std::mutex> mg(fused_mu_);  // see kge_step_fused_impl
+      const bool plain = fused_plain_ok(st);
+      uint32_t *tags = nullptr, *bits = nullptr;
+      if (plain) {
+        tags = reinterpret_cast<uint32_t*>(fused_tags_.data_ptr<int32_t>());
+        bits = tags + 32 * rowtag_words(num_keys_);
+      } else {
+        mg.unlock();
+      }
+      sk = upload_keys(name, hk, tags, kn, n_dev);
+      if (!us) kn = sk.ptr[3];
+      if (plain) {
+        RowTagKeys tk{{sk.ptr[0], kn, nullptr, nullptr}, {hk.blob.numel(), n_dev, 0, 0}, 2};
+        rowtag_flag_gpu(tags, tk, st);
+        rowtag_bits_gpu(tags, bits, tk, st);
+      }
+      kge_complex_step_chunk_fused_gpu(slab_.data, sk.ptr[0], sk.ptr[1], sk.ptr[2], kn,
+                                       loss.data_ptr<float>(), scratch.data_ptr<float>(), (int)B,
+                                       (int)C, (int)M, (int)D, Slab::padded(uniform_len_), world_,
+                                       (float)lr, (float)eps, st, bits);
+      (plain ? stat_fused_plain_ : stat_fused_atomic_) += 1;
+    }
+    count_fused_ops(3 * B + n_neg);
+    return {loss, drawn};
+  }
+
+  torch::Tensor kge_step_chunk_fused(torch::Tensor keys_s, torch::Tensor keys_r,
+                                     torch::Tensor keys_o, torch::Tensor keys_neg, int64_t C,
+                                     int64_t M, int64_t D, double lr, double eps) {
+    return std::get<0>(
+        kge_step_chunk_fused_impl(keys_s, keys_r, keys_o, &keys_neg, nullptr, C, M, D, lr, eps));
+  }
+
+  // Returns (loss, the ceil(B/C) * M drawn keys on the device).
+  std::tuple<torch::Tensor, torch::Tensor> kge_step_chunk_fused_sampled(
+      torch::Tensor keys_s, torch::Tensor keys_r, torch::Tensor keys_o, UniformStream& us,
+      int64_t C, int64_t M, int64_t D, double lr, double eps) {
+    return kge_step_chunk_fused_impl(keys_s, keys_r, keys_o, nullptr, &us, C, M, D, lr, eps);
+  }
+
   // The sides step with dropout (kernels.h, kge_complex_step_drop) on the
   // identity path: kge_step_sides_fused_impl pass for pass (the staged key
   // upload that is the tag pass, flag pass, bits pass, step), with the two
@@ -4539,6 +4640,42 @@ void kge_complex_step_sides(torch::Tensor s, torch::Tensor r, torch::Tensor o,
   }
 }
 
+// ComplEx step with chunk-shared negatives (kernels.h): chunks of C positives,
+// M negatives per chunk. B is loss.numel(); every tensor must have exactly the
+// rows the step reads or writes, and all of it is checked before anything is
+// enqueued.
+void kge_complex_step_chunk(torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::Tensor neg,
+                            torch::Tensor ds, torch::Tensor dr, torch::Tensor do_,
+                            torch::Tensor dneg, torch::Tensor loss, int64_t C, int64_t M,
+                            int64_t D, double lr, double eps) {
+  const char* name = "kge_complex_step_chunk";
+  for (auto* t : {&s, &r, &o, &neg, &ds, &dr, &do_, &dneg, &loss}) {
+    check_f32(*t, "kge tensor");
+    TORCH_CHECK(t->device() == s.device(), name, ": tensors on different devices");
+  }
+  check_chunk_shape(name, C, M, D, s.is_cuda());
+  const int64_t B = loss.numel(), row = 2 * D;
+  TORCH_CHECK(B < (int64_t)1 << 31, name, ": B = ", B, " is too large");
+  const int64_t n_chunks = (B + C - 1) / C;
+  for (auto* t : {&s, &r, &o, &ds, &dr, &do_})
+    TORCH_CHECK(t->numel() == B * row, name, ": s, r, o and their deltas must be [B][2D]");
+  for (auto* t : {&neg, &dneg})
+    TORCH_CHECK(t->numel() == n_chunks * M * row, name,
+                ": neg and dneg must be [ceil(B/C) * M][2D], ", n_chunks * M, " rows");
+  if (B == 0) return;
+  if (s.is_cuda()) {
+    TORCH_CHECK(hip_available(), name, ": CUDA tensor but no HIP device");
+    auto scratch = torch::empty({kge_chunk_scratch_floats(B, M)}, s.options());
+    kge_complex_step_chunk_gpu(cfp(s), cfp(r), cfp(o), cfp(neg), fp(ds), fp(dr), fp(do_),
+                               fp(dneg), fp(loss), fp(scratch), (int)B, (int)C, (int)M, (int)D,
+                               (float)lr, (float)eps, current_stream(s.device()));
+  } else {
+    kge_complex_step_chunk_cpu(cfp(s), cfp(r), cfp(o), cfp(neg), fp(ds), fp(dr), fp(do_),
+                               fp(dneg), fp(loss), (int)B, (int)C, (int)M, (int)D, (float)lr,
+                               (float)eps);
+  }
+}
+
 // ComplEx sides step with dropout (kernels.h): the sides step's tensors and
 // checks, plus the two dropout probabilities and the seed of the masks.
 void kge_complex_step_drop(torch::Tensor s, torch::Tensor r, torch::Tensor o,
@@ -5228,6 +5365,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::call_guard<py::gil_scoped_release>());
   m.def("kge_complex_step_drop", &kge_complex_step_drop,
         py::call_guard<py::gil_scoped_release>());
+  m.def("kge_complex_step_chunk", &kge_complex_step_chunk,
+        py::call_guard<py::gil_scoped_release>());
   m.def("alias_draw", &alias_draw, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step", &rescal_step, py::call_guard<py::gil_scoped_release>());
   m.def("rescal_step_grouped", &rescal_step_grouped, py::call_guard<py::gil_scoped_release>());
@@ -5267,6 +5406,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("CTR_SEG_CHUNK") = (int)CTR_SEG_CHUNK;
   m.attr("CTR_MAX_DIM") = (int)CTR_MAX_DIM;
   m.attr("RESCAL_FUSED_MAX_DIM") = (int)RESCAL_FUSED_MAX_DIM;
+  m.attr("KGE_CHUNK_MAX_C") = (int)KGE_CHUNK_MAX_C;
+  m.attr("KGE_CHUNK_MAX_M") = (int)KGE_CHUNK_MAX_M;
   m.attr("RESCAL_DROP_MAX_DIM") = (int)RESCAL_DROP_MAX_DIM;
   m.attr("W2V_WINDOW_MAX_DIM") = (int)W2V_WINDOW_MAX_DIM;
   m.attr("W2V_SCAN_BLOCK") = (int)W2V_SCAN_BLOCK;
@@ -5329,6 +5470,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       .def("kge_step_sides_fused_sampled", &Server::kge_step_sides_fused_sampled,
            py::call_guard<py::gil_scoped_release>())
       .def("kge_step_sides_fused_general", &Server::kge_step_sides_fused_general,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_chunk_fused", &Server::kge_step_chunk_fused,
+           py::call_guard<py::gil_scoped_release>())
+      .def("kge_step_chunk_fused_sampled", &Server::kge_step_chunk_fused_sampled,
            py::call_guard<py::gil_scoped_release>())
       .def("kge_step_drop_fused", &Server::kge_step_drop_fused,
            py::call_guard<py::gil_scoped_release>())

@@ -10,6 +10,7 @@
 // Push/Pull path. Kernels consume pulled rows and produce PUSH-ready
 // additive deltas: [delta_emb(D) | grad^2(D)].
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace adapm {
@@ -226,6 +227,60 @@ void kge_complex_step_drop_fused_offs_cpu(float* slab, const int64_t* offs_s,
                                           float* loss, int B, int N, int NS, int D, float lr,
                                           float eps, float gamma_e, float gamma_r, int thr_e,
                                           int thr_r, uint64_t drop_seed);
+
+// ComplEx step with CHUNK-SHARED negatives (kge_chunk_hip.hip). The batch of B
+// positives (s_b, r_b, o_b) is cut into chunks of C >= 1: n_chunks =
+// ceil(B / C), chunk c holds the positives [cC, min(B, (c+1)C)), so the last
+// chunk may be short. The negatives are n_chunks * M entity occurrences; chunk
+// c owns neg[cM .. cM + M) and every positive of the chunk is scored against
+// all M of them (the objective of PyTorch-BigGraph and DGL-KE; beyond the
+// reference, whose train() draws negatives per positive). Object side only,
+// no regulariser, no dropout. With c(b) = b / C:
+//   loss[b] = softplus(-psi(s_b, r_b, o_b)) + sum_{j<M} softplus(psi(s_b, r_b, n_{c(b),j}))
+// (softplus1pf on the GPU). With u_b = s_b * r_b as the real vector
+// [u_re | u_im], psi(s_b, r_b, x) = u_b . x, and
+//   g0_b = -sigmoid(-psi0_b),  G[b][j] = sigmoid(psi[b][j])
+//   a_b  = g0_b o_b + sum_j G[b][j] n_j         gradient w.r.t. u_b  (G N)
+//   g_s  = a_b * conj(r_b),  g_r = a_b * conj(s_b)   component-wise, as k_kge_step
+//   g_o  = g0_b u_b
+//   g_{n_j} = sum_{b in chunk} G[b][j] u_b      (G^T U)
+// Every row OCCURRENCE gets ONE AdaGrad update (adagrad_delta, accumulator +=
+// g^2) computed from the pre-step row: s, r and o one per positive, a negative
+// occurrence one update of its gradient summed over the chunk's positives (the
+// rule of R in the grouped RESCAL step). A key that occurs twice (twice in one
+// chunk, in two chunks, or as a negative and as some positive's s or o) is two
+// occurrences; on the slab they land hogwild, as for every fused step. With
+// C = 1 this is kge_complex_step with N = M.
+//  s, r, o, ds, dr, do_ [B][2D]; neg, dneg [n_chunks * M][2D]; loss [B]
+//  scratch: kge_chunk_scratch_floats(B, M) floats on the device, contents
+//  irrelevant (G [B][M], g0 [B], the loss shares [B][4])
+// Two launches on `stream` (scores, then update over (chunk, column block));
+// no atomic touches a partial sum, and a row unique in the batch is written
+// with plain stores when `bits` is given, so on unique keys the result does
+// not depend on scheduling. 1 <= C <= KGE_CHUNK_MAX_C, 1 <= M <=
+// KGE_CHUNK_MAX_M; the GPU entries need D % 8 == 0 (both halves of a row
+// 16-byte aligned, a K-chunk of 4 never straddles re and im) and loop over D,
+// so STEP_MAX_LANES does not bound it; the CPU twin takes any even D. Callers
+// check all of it. B < 1 is a no-op. The fused entry has the addressing modes
+// (row_at) and the `bits` contract of kge_complex_step_fused_gpu, the tags
+// covering s | r | o | neg.
+constexpr int KGE_CHUNK_MAX_C = 64;
+constexpr int KGE_CHUNK_MAX_M = 256;
+inline int64_t kge_chunk_scratch_floats(int64_t B, int64_t M) { return B * (M + 5); }
+// dynamic LDS of the update launch (150,528 B at the limits, of 163,840 B)
+size_t kge_chunk_update_lds_bytes(int C, int M);
+void kge_complex_step_chunk_gpu(const float* s, const float* r, const float* o, const float* neg,
+                                float* ds, float* dr, float* do_, float* dneg, float* loss,
+                                float* scratch, int B, int C, int M, int D, float lr, float eps,
+                                void* stream);
+void kge_complex_step_chunk_cpu(const float* s, const float* r, const float* o, const float* neg,
+                                float* ds, float* dr, float* do_, float* dneg, float* loss, int B,
+                                int C, int M, int D, float lr, float eps);
+void kge_complex_step_chunk_fused_gpu(float* slab, const int64_t* keys_s, const int64_t* keys_r,
+                                      const int64_t* keys_o, const int64_t* keys_neg, float* loss,
+                                      float* scratch, int B, int C, int M, int D, int32_t plen,
+                                      int world, float lr, float eps, void* stream,
+                                      const uint32_t* bits = nullptr);
 
 // CPU tier of the offsets-mode fused steps (exercises the world>1 fused
 // protocol path in the gloo multi-process tests; serial, in-place).

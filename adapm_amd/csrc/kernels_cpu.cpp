@@ -1149,4 +1149,67 @@ void w2v_window_step_cpu(float* slab, int32_t plen, const W2VWindowArgs& a, int 
   counts[0] = (int32_t)ww.ctok.size();
 }
 
+// Chunk-shared negatives (kernels.h, kge_complex_step_chunk), chunk by chunk
+// in the order of the contract: u and the scores of the chunk, then a_b and
+// the rows of every positive, then the negatives' summed gradients.
+void kge_complex_step_chunk_cpu(const float* s, const float* r, const float* o, const float* neg,
+                                float* ds, float* dr, float* do_, float* dneg, float* loss, int B,
+                                int C, int M, int D, float lr, float eps) {
+  const int dc = D >> 1;
+  const int64_t row = (int64_t)D << 1;
+  std::vector<float> U((size_t)C * D), G((size_t)C * M), g0(C), a(D), gn(D);
+  for (int b0 = 0, c = 0; b0 < B; b0 += C, ++c) {
+    const int Cc = std::min(C, B - b0);
+    const float* nc = neg + (int64_t)c * M * row;
+    for (int i = 0; i < Cc; ++i) {
+      const float* sb = s + (b0 + i) * row;
+      const float* rb = r + (b0 + i) * row;
+      const float* ob = o + (b0 + i) * row;
+      float* u = &U[(size_t)i * D];
+      for (int k = 0; k < dc; ++k) {
+        u[k] = sb[k] * rb[k] - sb[dc + k] * rb[dc + k];
+        u[dc + k] = sb[dc + k] * rb[k] + sb[k] * rb[dc + k];
+      }
+      double psi0 = 0.0;
+      for (int k = 0; k < D; ++k) psi0 += u[k] * ob[k];
+      g0[i] = -sigmoidf_(-(float)psi0);
+      float lsum = softplusf_(-(float)psi0);
+      for (int j = 0; j < M; ++j) {
+        double psi = 0.0;
+        for (int k = 0; k < D; ++k) psi += u[k] * nc[j * row + k];
+        G[(size_t)i * M + j] = sigmoidf_((float)psi);
+        lsum += softplusf_((float)psi);
+      }
+      loss[b0 + i] = lsum;
+    }
+    for (int i = 0; i < Cc; ++i) {
+      const int64_t b = b0 + i;
+      const float *sb = s + b * row, *rb = r + b * row, *ob = o + b * row;
+      const float* u = &U[(size_t)i * D];
+      for (int k = 0; k < D; ++k) a[k] = g0[i] * ob[k];
+      for (int j = 0; j < M; ++j)
+        for (int k = 0; k < D; ++k) a[k] += G[(size_t)i * M + j] * nc[j * row + k];
+      float *dsb = ds + b * row, *drb = dr + b * row, *dob = do_ + b * row;
+      for (int k = 0; k < dc; ++k) {
+        const float are = a[k], aim = a[dc + k];
+        write_delta_(&dsb[k], &dsb[D + k], are * rb[k] + aim * rb[dc + k], sb[D + k], lr, eps);
+        write_delta_(&dsb[dc + k], &dsb[D + dc + k], aim * rb[k] - are * rb[dc + k],
+                     sb[D + dc + k], lr, eps);
+        write_delta_(&drb[k], &drb[D + k], are * sb[k] + aim * sb[dc + k], rb[D + k], lr, eps);
+        write_delta_(&drb[dc + k], &drb[D + dc + k], aim * sb[k] - are * sb[dc + k],
+                     rb[D + dc + k], lr, eps);
+      }
+      for (int k = 0; k < D; ++k) write_delta_(&dob[k], &dob[D + k], g0[i] * u[k], ob[D + k], lr, eps);
+    }
+    for (int j = 0; j < M; ++j) {
+      std::fill(gn.begin(), gn.end(), 0.f);
+      for (int i = 0; i < Cc; ++i)
+        for (int k = 0; k < D; ++k) gn[k] += G[(size_t)i * M + j] * U[(size_t)i * D + k];
+      float* dnb = dneg + ((int64_t)c * M + j) * row;
+      for (int k = 0; k < D; ++k)
+        write_delta_(&dnb[k], &dnb[D + k], gn[k], nc[j * row + D + k], lr, eps);
+    }
+  }
+}
+
 }  // namespace adapm

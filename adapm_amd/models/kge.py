@@ -18,6 +18,10 @@ Rebuild of the reference app (reference apps/knowledge_graph_embeddings.cc):
     hash of a per-step seed computed inside the step kernels
     (k_kge_step_drop, and k_rescal_drop for Rescal; csrc/kernels.h has
     both contracts). Evaluation never drops.
+  - chunk-shared negatives, opt-in and beyond the reference (neg_chunk:
+    chunks of that many positives share one draw of neg_samples
+    negatives; k_chunk_scores / k_chunk_update, MFMA GEMMs per chunk;
+    csrc/kernels.h, kge_complex_step_chunk).
   - eval: MRR / Hits@k by scoring candidate sets (reference :544-712)
   - checkpoint: WaitSync -> Barrier -> rank-0 full pull -> save
     (reference :327-401)
@@ -62,6 +66,23 @@ class ComplExConfig:
     # 1/1024 after rounding, at most 1023/1024.
     dropout_entity: float = 0.0    # on the subject and object rows
     dropout_relation: float = 0.0  # on the relation row
+    # chunk-shared negatives (csrc/kernels.h, kge_complex_step_chunk): the
+    # batch is cut into chunks of neg_chunk positives and each chunk shares
+    # ONE draw of neg_samples negatives. 0: negatives per positive, as ever.
+    # ComplEx only, and not together with the sides or dropout settings.
+    neg_chunk: int = 0
+
+    def chunk_negatives(self, B: int) -> int:
+        """Negative keys of a step over B positives with neg_chunk set."""
+        return -(-B // self.neg_chunk) * self.neg_samples
+
+    def check_neg_chunk(self):
+        if self.neg_chunk < 0:
+            raise ValueError(f"neg_chunk = {self.neg_chunk} must be >= 0")
+        if self.neg_chunk and (self.sides or self.dropout):
+            raise ValueError(
+                "neg_chunk cannot be combined with neg_samples_subject, gamma_entity, "
+                "gamma_relation, dropout_entity or dropout_relation")
 
     @property
     def sides(self) -> bool:
@@ -111,6 +132,10 @@ class ComplEx(StepModel):
 
     # ------------------------------------------------------------ init
 
+    def __init__(self, cfg, server, worker):
+        cfg.check_neg_chunk()
+        super().__init__(cfg, server, worker)
+
     def init_embeddings(self):
         """Each rank initializes the keys it manages (key % world == rank)
         with set(); AdaGrad accumulators start at 0."""
@@ -135,6 +160,8 @@ class ComplEx(StepModel):
         """One draw per step. The sides step splits it: the first
         B * neg_samples keys corrupt the object, the rest the subject."""
         cfg = self.cfg
+        if cfg.neg_chunk:  # one draw of neg_samples keys per chunk
+            return self._negatives(cfg.chunk_negatives(B), cfg.num_entities)
         return self._negatives(B * (cfg.neg_samples + cfg.neg_samples_subject),
                                cfg.num_entities)
 
@@ -160,8 +187,15 @@ class ComplEx(StepModel):
         has the seed)."""
         return (*self._sides_tail(), *_drop_tail(self))
 
+    def _chunk_tail(self):
+        cfg = self.cfg
+        return cfg.neg_chunk, cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps
+
     def _launch(self, v, d, loss):
         cfg = self.cfg
+        if cfg.neg_chunk:  # v, d: s | r | o | the chunks' negatives
+            _C.kge_complex_step_chunk(*v, *d, loss, *self._chunk_tail())
+            return
         if cfg.dropout:  # v, d: s | r | o | neg_o | neg_s
             _C.kge_complex_step_drop(*v, *d, loss, *self._drop_tail())
             return
@@ -218,8 +252,35 @@ class ComplEx(StepModel):
                     torch.from_numpy(np.ascontiguousarray(negs2.reshape(-1))),
                     cfg.neg_samples, cfg.dim, cfg.lr, cfg.eps)
 
+    def _train_batch_chunk_fused(self, triples, sync_loss, neg_keys):
+        """train_batch_fused with cfg.neg_chunk: the slab-direct chunk step
+        on the identity path (negatives drawn on the device when the
+        sampling manager has a device stream), train_batch on every other
+        store. A chunk's negatives belong to its position in the batch,
+        so there is no offsets-mode path whose misses would move them."""
+        cfg = self.cfg
+        w = self.worker
+        if not self._fused_identity(False):
+            return self.train_batch(triples, sync_loss=sync_loss, neg_keys=neg_keys)
+        raw = self.server.raw
+        keys = tuple(map(torch.from_numpy, self.keys_of(triples)))
+        smp = self.server.sampling
+        if (neg_keys is None and smp is not None and not _HOST_NEGATIVES
+                and smp.device_stream() is not None):
+            NN = cfg.chunk_negatives(len(triples))
+            sid = w.prepare_sample(NN, w.current_clock(), w.current_clock() + 2)
+            us = smp.pull_device(w, sid, NN, draw=False)
+            w.finish_sample(sid)
+            loss, _neg = raw.kge_step_chunk_fused_sampled(*keys, us, *self._chunk_tail())
+            return self._loss_out(loss, sync_loss)
+        if neg_keys is None:
+            neg_keys = self._draw_negatives(len(triples))
+        neg = torch.from_numpy(np.ascontiguousarray(neg_keys, dtype=np.int64))
+        return self._loss_out(raw.kge_step_chunk_fused(*keys, neg, *self._chunk_tail()),
+                              sync_loss)
+
     def train_batch_fused(self, triples: np.ndarray, sync_loss: bool = False,
-                          force_general: bool = False):
+                          force_general: bool = False, neg_keys: np.ndarray = None):
         """Fused slab-direct step: kernels read rows straight from the
         HBM slab and accumulate the AdaGrad deltas back — no pull/push
         buffers. world==1 with the identity layout uses the zero-host-
@@ -228,8 +289,11 @@ class ComplEx(StepModel):
         runs the fused kernel on the samples whose keys are all local
         (>95% after intent-driven relocation) and routes the rest
         through the classic pull/kernel/push path. force_general also
-        enables the general path on the CPU store (the gloo test tier)."""
+        enables the general path on the CPU store (the gloo test tier).
+        neg_keys names the negatives of the chunk step (cfg.neg_chunk)."""
         cfg = self.cfg
+        if cfg.neg_chunk:
+            return self._train_batch_chunk_fused(triples, sync_loss, neg_keys)
         w = self.worker
         B = len(triples)
         smp = self.server.sampling
@@ -507,6 +571,9 @@ def main():
                     help="dropout on the subject and object rows (reference: --dropout_entity)")
     ap.add_argument("--dropout-relation", type=float, default=0.0,
                     help="dropout on the relation row (reference: --dropout_relation)")
+    ap.add_argument("--neg-chunk", type=int, default=0,
+                    help="share one draw of --neg negatives among this many positives "
+                         "(0: negatives per positive)")
     ap.add_argument("--triples", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--epochs", type=int, default=2)
@@ -530,7 +597,8 @@ def main():
                         neg_samples=a.neg, batch_size=a.batch, lr=a.lr,
                         neg_samples_subject=a.neg_samples_subject,
                         gamma_entity=a.gamma_entity, gamma_relation=a.gamma_relation,
-                        dropout_entity=a.dropout_entity, dropout_relation=a.dropout_relation)
+                        dropout_entity=a.dropout_entity, dropout_relation=a.dropout_relation,
+                        neg_chunk=a.neg_chunk)
     model = ComplEx(cfg, server, worker)
     model.init_embeddings()
     rank = server.my_rank()
@@ -585,6 +653,12 @@ class Rescal(StepModel):
     masks per scored triple, seeded per launch as ComplEx seeds them."""
 
     _drop_steps = 0  # drop launches so far: the step counter of drop_seed
+
+    def __init__(self, cfg, server, worker):
+        if cfg.neg_chunk:
+            raise ValueError("neg_chunk is a ComplEx setting: Rescal has no step with "
+                             "chunk-shared negatives")
+        super().__init__(cfg, server, worker)
 
     @staticmethod
     def value_lengths(num_entities, num_relations, dim):

@@ -36,6 +36,7 @@ SOURCES = [
     "ctr_hip.hip",
     "rescal_fused_hip.hip",
     "kge_drop_hip.hip",
+    "kge_chunk_hip.hip",
     "rescal_drop_hip.hip",
     "w2v_window_hip.hip",
     "kernels_cpu.cpp",
@@ -43,13 +44,15 @@ SOURCES = [
 
 # Per-source flags. ctr_hip.hip adds float4 lanes element by element; it,
 # rescal_fused_hip.hip, kge_drop_hip.hip, rescal_drop_hip.hip (float4 column
-# sums, element by element) and w2v_window_hip.hip (float4 lanes of a row)
+# sums, element by element), w2v_window_hip.hip (float4 lanes of a row) and
+# kge_chunk_hip.hip (u = s * r formed on float4 lanes, element by element)
 # are built without the packed fp32 instructions.
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "ctr_hip.hip": NO_PACKED_FP32,
     "rescal_fused_hip.hip": NO_PACKED_FP32,
     "kge_drop_hip.hip": NO_PACKED_FP32,
+    "kge_chunk_hip.hip": NO_PACKED_FP32,
     "rescal_drop_hip.hip": NO_PACKED_FP32,
     "w2v_window_hip.hip": NO_PACKED_FP32,
 }
